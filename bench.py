@@ -7,7 +7,11 @@ ball_query, grouping, grouped MLP, three_nn, three_interpolate, FP MLPs, head) -
 is sharded per rank (B=32 per GPU, weak scaling) and the only collective is one flat gradient all-reduce over
 RCCL per step (torch_points3d_amd/dp.py).  Rank 0 prints ONE JSON line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else, after the timed
+region: the per-kernel HIP-event pass (roofline, north-star kernels, side file), the CPU baselines, the forward-only
+line and, with N > 1, the collective timed on its own.  --dump-outputs DIR writes what the last timed step computed.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full [--no-cpu-baseline]] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -345,7 +349,7 @@ def headline_json(line):
 def emit(line, detail, args):
     """Heavy tables (per-shape kernels, per-entry sums, north-star rows with their counters) go to a side file; the
     headline object is the LAST stdout line."""
-    path = getattr(args, "details_out", None) or os.path.join(ROOT, "gpurun_out", "bench_detail_%s.json" % args.workload)
+    path = getattr(args, "details_out", None) or os.path.join(ROOT, "bench_out", "bench_detail_%s.json" % args.workload)
     if detail is not None:
         try:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -358,6 +362,32 @@ def emit(line, detail, args):
     sys.stdout.flush()
     sys.stdout.write(headline_json(line) + "\n")
     sys.stdout.flush()
+
+
+DUMP_LIMIT = 60 * 10 ** 6  # bytes: all files of one --dump-outputs together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as PATH/<name>.npy, float32 (float64 for integer or double data).  When the arrays
+    together exceed DUMP_LIMIT, each one larger than its even share of it is replaced by a fixed sample of its
+    flattened elements (seeded: the same positions on every run), so that two builds compare output for output."""
+    import numpy as np
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if (t.dtype == torch.float64 or not t.is_floating_point()) else t.float()
+        out[name] = t.cpu().numpy()
+    if sum(a.nbytes for a in out.values()) > DUMP_LIMIT:
+        share = DUMP_LIMIT // len(out)
+        for name, a in out.items():
+            if a.nbytes > share:
+                sel = torch.randperm(a.size, generator=torch.Generator().manual_seed(0))[:share // a.itemsize]
+                out[name] = a.reshape(-1)[sel.sort().values.numpy()]
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log("outputs of the last timed step written to %s (%s)" % (path, ", ".join(
+        "%s %s" % (k, "x".join(map(str, a.shape))) for k, a in out.items())))
 
 
 def cpu_share():
@@ -409,7 +439,8 @@ def cpu_baseline(sample_b, iters):
 
 
 def time_forward(model, pos, x, steps, warmup, use_graph):
-    """seconds for `steps` forward passes (train-mode BatchNorm, no autograd), replayed from one HIP graph if possible"""
+    """seconds for `steps` forward passes (train-mode BatchNorm, no autograd), replayed from one HIP graph if possible;
+    also returns the scores of the last pass"""
     with torch.no_grad():
         for _ in range(max(warmup, 1)):
             model(pos, x)
@@ -425,19 +456,19 @@ def time_forward(model, pos, x, steps, warmup, use_graph):
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    model(pos, x)
+                    static_out = model(pos, x)
                 graphed = True
             except Exception as exc:  # noqa: BLE001 -- capture is an optimisation; eager launches measure the same kernels
                 log("graph capture unavailable (%s: %s); eager launches" % (type(exc).__name__, exc))
                 torch.cuda.synchronize()
-        step = g.replay if graphed else (lambda: model(pos, x))
-        step()
+        step = (lambda: (g.replay(), static_out)[1]) if graphed else (lambda: model(pos, x))
+        out = step()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            step()
+            out = step()
         torch.cuda.synchronize()
-        return time.perf_counter() - t0, graphed
+        return time.perf_counter() - t0, graphed, out
 
 
 def cpu_forward_baseline(sample_b, iters):
@@ -518,7 +549,19 @@ def run_forward(args):
     torch.cuda.set_device(device)
     model = build_model(None, device)
     pos, x, _ = make_inputs(B_PER_GPU, N_POINTS, 1234, device)
-    dt, graphed = time_forward(model, pos, x, args.steps, args.warmup, not args.no_graph)
+    dt, graphed, out = time_forward(model, pos, x, args.steps, args.warmup, not args.no_graph)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"scores": out})
+    value = B_PER_GPU * args.steps / dt
+    line = {"metric": "point-clouds/sec forward PointNet++SSG B=32 N=16384", "value": round(value, 2),
+            "unit": "point-clouds/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "PointNet++ SSG (%s) forward, train-mode BatchNorm, B=32, N=16384, FEAT=3, 10 classes, "
+                                   "pos~U[-1,1]^3 (BASELINE configs[1])" % MODEL_CONFIG,
+                       "launch": "hip-graph replay" if graphed else "eager"}}
+    if not args.full:
+        return emit(line, None, args)
     with torch.no_grad():
         # per-entry HIP-event timing in an eager pass outside the timed region
         timer = _lib.KernelTimer()
@@ -550,15 +593,7 @@ def run_forward(args):
                "sample": "%d forward passes of the same PointNet++ SSG on %d clouds of N=%d after 1 warm-up; PyTorch-CPU "
                          "conv/BN + oracle/tpk_ref_cpu.c kernels (OpenMP over clouds/queries)" % (iters, cb, N_POINTS),
                "seconds": cdt}
-    value = B_PER_GPU * args.steps / dt
-    line = {"metric": "point-clouds/sec forward PointNet++SSG B=32 N=16384", "value": round(value, 2),
-            "unit": "point-clouds/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "PointNet++ SSG (%s) forward, train-mode BatchNorm, B=32, N=16384, FEAT=3, 10 classes, "
-                                   "pos~U[-1,1]^3 (BASELINE configs[1])" % MODEL_CONFIG,
-                       "launch": "hip-graph replay" if graphed else "eager"},
-            "roofline": roofline, "cpu_baseline": cpu}
+    line.update(roofline=roofline, cpu_baseline=cpu)
     if cpu:
         line["gpu_over_cpu"] = round(value / cpu["value"], 1)
     emit(line, {"entry_points": entries, "north_star_kernels": north_star_kernels(timer.summary())}, args)
@@ -599,6 +634,17 @@ def run_kpconv(args):
         out = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"scores": out.x})
+    line = {
+        "metric": "points/sec KPConv unet_4 forward N=65536", "value": round(n * args.steps / dt, 1), "unit": "points/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "KPConv rigid segmentation forward (applications/kpconv.py unet_4, in_feat 64, grid 0.02, 25 "
+                               "neighbours, 13 classes), one cloud of 65536 points (BASELINE configs[3]); sampling and "
+                               "searches inside the timed region", "launch": "eager"}}
+    if not args.full:
+        return emit(line, None, args)
     _lib.set_timer(timer)
     for _ in range(args.steps):
         step()
@@ -625,15 +671,9 @@ def run_kpconv(args):
                 "sample": "1 forward of the same model on the same cloud: reference block logic mirrored on the CPU with "
                           "oracle/tpk_ref_cpu.c radius search + kNN, oracle/voxel_ref.py grid sampling, PyTorch-CPU "
                           "KPConv_ops / Linear / BatchNorm", "seconds": sec, "max_rel_diff_vs_gpu": err}
-    emit({
-        "metric": "points/sec KPConv unet_4 forward N=65536", "value": round(n * args.steps / dt, 1), "unit": "points/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "KPConv rigid segmentation forward (applications/kpconv.py unet_4, in_feat 64, grid 0.02, 25 "
-                               "neighbours, 13 classes), one cloud of 65536 points (BASELINE configs[3]); sampling and "
-                               "searches inside the timed region", "launch": "eager"},
-        "roofline": roof, "cpu_baseline": base},
-        {"entry_points": entry_table(per_entry, args.steps), "kernels": shape_table(timer.summary(), args.steps)}, args)
+    line.update(roofline=roof, cpu_baseline=base)
+    emit(line, {"entry_points": entry_table(per_entry, args.steps), "kernels": shape_table(timer.summary(), args.steps)},
+         args)
 
 
 def run_knn(args):
@@ -669,7 +709,18 @@ def run_knn(args):
         idx, q, (nbr, d2) = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"sample": idx, "queries": q, "neighbours": nbr, "dist2": d2})
     nq = q.shape[0]
+    line = {
+        "metric": "queries/sec random-subsample + exact 16-NN, N=10^6", "value": round(nq * args.steps / dt, 1),
+        "unit": "queries/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "RandLA-Net sampling + neighbour search leg (BASELINE configs[4]): one room-shaped scene of "
+                               "10^6 surface points, 250000 queries drawn with replacement, k = 16", "launch": "eager"}}
+    if not args.full:
+        return emit(line, None, args)
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     by = batch[idx]
     a.record()
@@ -698,14 +749,8 @@ def run_knn(args):
         base = {"value": sel.numel() / sec, "unit": "queries/s", "cores": threads, "kind": "port",
                 "sample": "%d of the %d queries, brute force over the 10^6 points (oracle/tpk_ref_cpu.c, OpenMP over "
                           "queries)" % (sel.numel(), nq), "seconds": sec, "gpu_result_identical_on_sample": same}
-    emit({
-        "metric": "queries/sec random-subsample + exact 16-NN, N=10^6", "value": round(nq * args.steps / dt, 1),
-        "unit": "queries/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "RandLA-Net sampling + neighbour search leg (BASELINE configs[4]): one room-shaped scene of "
-                               "10^6 surface points, 250000 queries drawn with replacement, k = 16", "launch": "eager"},
-        "roofline": roof, "cpu_baseline": base}, {}, args)
+    line.update(roofline=roof, cpu_baseline=base)
+    emit(line, {}, args)
 
 
 def main():
@@ -714,7 +759,13 @@ def main():
     # (defaults: the timed region's fixed cost -- two barriers, two device synchronisations -- is ~1 ms, 0.6 % of 20 steps)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything the headline figure does not need: per-kernel "
+                         "HIP-event pass (roofline, north-star kernels, side file), CPU baselines, forward-only line, "
+                         "collective timed on its own")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-sample-clouds", type=int, default=8)
     ap.add_argument("--cpu-sample-iters", type=int, default=8)
     ap.add_argument("--model", default="unet_3_ss", choices=["unet_3_ss", "unet_4_ss", "unet_3_ms"],
@@ -749,8 +800,9 @@ def main():
                          "their (B*N, classes) view (no transposing copies, but PyTorch's row soft-max is 0.7 ms slower on "
                          "10-wide rows -- measured, kept as a switch)")
     ap.add_argument("--details-out", default=None, metavar="PATH",
-                    help="side file for the heavy tables (per-shape kernels, per-entry sums, north-star rows); default "
-                         "gpurun_out/bench_detail_<workload>.json.  The headline stays the last stdout line, < 4 KB")
+                    help="with --full: side file for the heavy tables (per-shape kernels, per-entry sums, north-star "
+                         "rows); default bench_out/bench_detail_<workload>.json.  The headline stays the last stdout "
+                         "line, < 4 KB")
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE",
                     help="experiment switch: set an attribute of torch_points3d_amd.fused (e.g. USE_MLP_CHAIN=0) before the "
                          "run; recorded in the JSON line")
@@ -822,14 +874,24 @@ def main():
                                                foreach=args.adam == "foreach", capturable=use_graph)
     global LOSS_ROWS
     LOSS_ROWS = args.loss_layout == "rows"
+    # (scores, loss) of the latest training pass through each geometry slot; once the step is captured these are the
+    # graphs' own output tensors, which every replay rewrites (--dump-outputs reads the last step's).  Kept detached:
+    # a kept autograd graph would carry the warm-up's gradient accumulators into the side-stream capture.
+    passes = {}
+
+    def scored_loss(scores, slot):
+        loss = seg_loss(scores, y)
+        passes[slot] = (scores.detach(), loss.detach())
+        return loss
+
     if args.no_geometry_prefetch or not hasattr(model.net, "precompute_geometry"):
-        trainer = ShardedStep(model, make_opt, lambda: seg_loss(model(pos, x), y), world_size=world,
+        trainer = ShardedStep(model, make_opt, lambda: scored_loss(model(pos, x), 0), world_size=world,
                               use_graph=use_graph, log=log, reduce_always=multi)
     else:
         # sampling / radius searches / 3-NN tables of step i+1 run on a second stream during step i (dp.PipelinedStep)
         net = model.net
         trainer = PipelinedStep(model, make_opt, lambda slot: net.precompute_geometry(pos, backward_tables=True),
-                                lambda geo: seg_loss(model(pos, x, geometry=geo), y),
+                                lambda geo: scored_loss(model(pos, x, geometry=geo), trainer._cur),
                                 world_size=world, use_graph=use_graph, log=log, reduce_always=multi)
     log("model built; warm-up")
     graphed = trainer.warmup_and_capture(args.warmup)
@@ -841,7 +903,7 @@ def main():
     if multi:
         dist.barrier()
     torch.cuda.synchronize()
-    if not graphed:
+    if not graphed and args.full:
         _lib.set_timer(timer)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -853,7 +915,13 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     _lib.set_timer(None)
-    if graphed and rank == 0:
+    if args.dump_outputs and rank == 0:
+        # the PipelinedStep has moved on to the other slot after the last step
+        scores, loss = passes[trainer._cur ^ 1 if isinstance(trainer, PipelinedStep) else 0]
+        dump_outputs(args.dump_outputs, {
+            "scores": scores, "loss": loss, "params": trainer.flat_param.detach(), "grads": trainer.flat,
+            "buffers": torch.cat([b.detach().double().reshape(-1) for b in model.buffers()])})
+    if graphed and rank == 0 and args.full:
         # per-kernel HIP-event timing needs eager launches: the same K steps again, outside the headline region
         # (rank 0 only; no collective is involved in this pass)
         saved = (trainer.world, trainer.reduce_always)
@@ -873,6 +941,7 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if multi and args.full:
         # the step's only collective, timed on its own (device events around K all-reduce + divide rounds)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
@@ -885,28 +954,8 @@ def main():
         coll_ms = round(e0.elapsed_time(e1) / args.steps, 4)
 
     if rank == 0:
-        summ = timer.summary()
-        kernels = shape_table(summ, args.steps)
-        per_entry = entry_sums(summ)
-        roofline = dominant_roofline(per_entry, args.steps)
-        entries = entry_table(per_entry, args.steps)
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu = cpu_baseline(args.cpu_sample_clouds, args.cpu_sample_iters)
-        # the north star's ">= 30x the CPU path" is defined on the SSG FORWARD pass: measured in the same run, after the
-        # headline region (BASELINE configs[1] as written; train-mode BatchNorm as the reference's example)
-        forward_only = None
-        if world == 1:
-            fdt, fgraphed = time_forward(model, pos, x, args.steps, 2, use_graph)
-            forward_only = {"ms_per_step": round(fdt / args.steps * 1e3, 3), "value": round(b_rank * args.steps / fdt, 2),
-                            "unit": "point-clouds/s", "launch": "hip-graph replay" if fgraphed else "eager"}
-            if not args.no_cpu_baseline:
-                fcpu = cpu_forward_baseline(args.cpu_sample_clouds, max(args.cpu_sample_iters // 2, 2))
-                forward_only["cpu_baseline"] = fcpu
-                forward_only["gpu_over_cpu"] = round(forward_only["value"] / fcpu["value"], 1)
         value = world * b_rank * args.steps / dt
         grouping = "MSG" if (MODEL_CONFIG.endswith("_ms") or args.workload == "msg_c3") else "SSG"
-        ns_rows = north_star_kernels(summ)  # the per-kernel pass runs on one stream: spatial kernels timed on their own
         line = {
             "metric": "point-clouds/sec fwd+bwd PointNet++%s B=32 N=%d" % (grouping, N_POINTS),
             "value": round(value, 2),
@@ -927,19 +976,40 @@ def main():
                            "" if args.no_geometry_prefetch else "; geometry of step i+1 on a 2nd stream during step i"),
                        "global_batch": world * b_rank, "points": N_POINTS,
                        "parallelism": "dp%d, whole clouds per rank, one flat gradient all-reduce (RCCL) per step" % world},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "forward_only": forward_only,
-            "north_star": north_star_summary(ns_rows),
         }
-        if multi:
-            line["collective"] = {"what": "flat fp32 gradient all-reduce + divide per step (RCCL)",
-                                  "bytes": int(trainer.flat.numel() * 4), "ms_per_step": coll_ms}
         if args.set:
             line["experiment_switches"] = args.set
-        if cpu:
-            line["gpu_over_cpu"] = round(value / cpu["value"], 1)
-        emit(line, {"north_star_kernels": ns_rows, "entry_points": entries, "kernels": kernels}, args)
+        if not args.full:
+            emit(line, None, args)
+        else:
+            summ = timer.summary()
+            kernels = shape_table(summ, args.steps)
+            per_entry = entry_sums(summ)
+            entries = entry_table(per_entry, args.steps)
+            cpu = None
+            if world == 1 and not args.no_cpu_baseline:
+                cpu = cpu_baseline(args.cpu_sample_clouds, args.cpu_sample_iters)
+            # the north star's ">= 30x the CPU path" is defined on the SSG FORWARD pass: measured in the same run, after
+            # the headline region (BASELINE configs[1] as written; train-mode BatchNorm as the reference's example)
+            forward_only = None
+            if world == 1:
+                fdt, fgraphed, _ = time_forward(model, pos, x, args.steps, 2, use_graph)
+                forward_only = {"ms_per_step": round(fdt / args.steps * 1e3, 3),
+                                "value": round(b_rank * args.steps / fdt, 2), "unit": "point-clouds/s",
+                                "launch": "hip-graph replay" if fgraphed else "eager"}
+                if not args.no_cpu_baseline:
+                    fcpu = cpu_forward_baseline(args.cpu_sample_clouds, max(args.cpu_sample_iters // 2, 2))
+                    forward_only["cpu_baseline"] = fcpu
+                    forward_only["gpu_over_cpu"] = round(forward_only["value"] / fcpu["value"], 1)
+            ns_rows = north_star_kernels(summ)  # the per-kernel pass runs on one stream: spatial kernels timed on their own
+            line.update(roofline=dominant_roofline(per_entry, args.steps), cpu_baseline=cpu, forward_only=forward_only,
+                        north_star=north_star_summary(ns_rows))
+            if multi:
+                line["collective"] = {"what": "flat fp32 gradient all-reduce + divide per step (RCCL)",
+                                      "bytes": int(trainer.flat.numel() * 4), "ms_per_step": coll_ms}
+            if cpu:
+                line["gpu_over_cpu"] = round(value / cpu["value"], 1)
+            emit(line, {"north_star_kernels": ns_rows, "entry_points": entries, "kernels": kernels}, args)
     if multi:
         dist.barrier()
         dist.destroy_process_group()

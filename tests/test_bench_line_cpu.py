@@ -129,3 +129,44 @@ def test_north_star_counters_attach_per_shape_only(tmp_path, monkeypatch):
     rows = bench.north_star_kernels(canned_summary())
     with_counters = [r for r in rows if "counters" in r]
     assert len(with_counters) == 1 and with_counters[0]["sizes"][:4] == [32, 16384, 512, 64]
+
+
+def test_dump_outputs_fit_the_budget_and_sample_fixed_positions(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files, together under the budget; an array too large for its share is a
+    sample taken at the same positions on every run, so that two builds can be compared element for element"""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 6000)
+    arrays = {"scores": torch.arange(3000, dtype=torch.float32).reshape(30, 100), "ids": torch.arange(10),
+              "loss": torch.tensor(1.5)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    assert sorted(os.listdir(tmp_path / "a")) == ["ids.npy", "loss.npy", "scores.npy"]
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in arrays}
+    assert sum(a.nbytes for a in got.values()) <= 6000
+    assert got["ids"].dtype == np.float64 and np.array_equal(got["ids"], np.arange(10))
+    assert got["loss"].dtype == np.float32 and float(got["loss"]) == 1.5
+    s = got["scores"]
+    assert s.dtype == np.float32 and 0 < s.size < 3000 and np.all(np.diff(s) > 0)  # sorted positions, no repeats
+    assert np.array_equal(s, np.load(tmp_path / "b" / "scores.npy"))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_given_steps_and_dumps_outputs(tmp_path):
+    """a plain run: the headline line alone (no side file, no CPU baseline), `steps` timed steps, and the last step's
+    scores, loss, parameters, gradients and BatchNorm buffers in --dump-outputs"""
+    import subprocess
+    import numpy as np
+    out = tmp_path / "dump"
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                           "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert proc.returncode == 0, proc.stderr[-3000:]
+    line = json.loads(proc.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["unit"] == "point-clouds/s"
+    assert line["value"] == pytest.approx(32 * 1e3 / line["ms_per_step"], rel=1e-2)
+    assert "details" not in line and "cpu_baseline" not in line and "roofline" not in line
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert set(got) == {"scores", "loss", "params", "grads", "buffers"}
+    assert got["scores"].shape == (32, 10, 16384) and got["loss"].shape == ()
+    assert sum(a.nbytes for a in got.values()) < 64 * 10 ** 6
+    assert all(np.isfinite(a).all() for a in got.values())
