@@ -72,6 +72,10 @@ WGRAD_X3_ACT = True  # ... and its loader waves form the activated A operand fro
 WGRAD_X3 = 6  # weight-gradient contractions of the large layers on the bf16 matrix pipe, every fp32 value split exactly into
               # three bf16 terms (csrc/gemm_tn_x3.hip): 6 = the six term pairs of weight >= 2^-15 (what is dropped is below
               # 2^-21 of a product), 9 = all nine (every product exact), 0 = the fp32 MFMA kernel for every shape.
+              # The split truncates, so the dropped pairs have the sign of a * b: on one-signed operands (abs(randn), post-
+              # LeakyReLU rows against a dY with a common offset) the six-term result sits 4.1-4.4e-8 of |dY|^T |A| below
+              # float64 on average (nine terms and fp32 MFMA: <= 7e-9), while the largest element error stays within
+              # 0.9-1.25x the fp32 MFMA kernel's (2.5-2.8e-7 of |dY|^T |A|) -- test_x3_weight_gradient_on_one_signed_operands.
               # Measured against float64 on the layers of the BASELINE step: 2.1-3.3e-7 of the scale with 6 or 9 terms
               # (hi * hi products in an accumulator of their own), 4.2-5.4e-7 for the fp32 MFMA kernel; 524288 x 128 x 128:
               # 133 us (6), 141 us (9), 185 us (fp32 MFMA) -- the matrix pipe's load lowers the shader clock (2.2 -> 1.8 GHz
