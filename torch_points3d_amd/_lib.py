@@ -74,9 +74,33 @@ SIGNATURES = {
     "tp3d_bn_plan": [_l, _i, _i, _p],
     "tp3d_scatter_plan": [_i, _i, _i, _i, _p],
 }
-MISC = ("tp3d_abi_version", "tp3d_strerror", "tp3d_last_hip_error", "tp3d_scatter_workspace_bytes",
-        "tp3d_bn_workspace_floats", "tp3d_gemm_tn_workspace_floats", "tp3d_gemm_tn_x3_workspace_floats", "tp3d_gemm_tn_x3_serves", "tp3d_gemm_tn_x3_red_chunks", "tp3d_ball_query_workspace_bytes",
-        "tp3d_gemm_rows_stat_floats", "tp3d_gemm_rows_stat_chunks", "tp3d_gemm_rows_sp_chunks", "tp3d_gemm_rows_x3_chunks", "tp3d_gemm_rows_bnbwd_sp_serves", "tp3d_gemm_tn_bn_narrow_serves", "tp3d_gemm_rows_narrow_chunks", "tp3d_gemm_tn_bn_narrow_workspace_floats", "tp3d_gemm_rows_workspace_floats", "tp3d_kpconv_bwd_workspace_bytes", "tp3d_voxel_workspace_bytes", "tp3d_knn_workspace_bytes", "tp3d_kpconv_grad_workspace_bytes")
+_z = ctypes.c_size_t
+# name -> (restype, argtypes): version / error reporting and the host-side size and shape queries
+MISC = {
+    "tp3d_abi_version": (_i, []),
+    "tp3d_strerror": (ctypes.c_char_p, [_i]),
+    "tp3d_last_hip_error": (_i, []),
+    "tp3d_scatter_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "tp3d_bn_workspace_floats": (_z, [_l, _i]),
+    "tp3d_gemm_tn_workspace_floats": (_z, [_l, _i, _i]),
+    "tp3d_gemm_tn_x3_workspace_floats": (_z, [_l, _i, _i]),
+    "tp3d_gemm_tn_x3_serves": (_i, [_l, _i, _i]),
+    "tp3d_gemm_tn_x3_red_chunks": (_i, [_l, _i, _i]),
+    "tp3d_kpconv_bwd_workspace_bytes": (_z, [_l, _l]),
+    "tp3d_gemm_rows_stat_floats": (_z, [_l, _i]),
+    "tp3d_gemm_rows_stat_chunks": (_i, [_l, _i]),
+    "tp3d_gemm_rows_narrow_chunks": (_i, [_l]),
+    "tp3d_gemm_tn_bn_narrow_serves": (_i, [_l, _i, _i]),
+    "tp3d_gemm_tn_bn_narrow_workspace_floats": (_z, [_l, _i, _i]),
+    "tp3d_gemm_rows_bnbwd_sp_serves": (_i, [_l, _i, _i]),
+    "tp3d_gemm_rows_x3_chunks": (_i, [_l, _i, _i, _i]),
+    "tp3d_gemm_rows_sp_chunks": (_i, [_l, _i, _i, _i]),
+    "tp3d_gemm_rows_workspace_floats": (_z, [_l, _i, _i]),
+    "tp3d_kpconv_grad_workspace_bytes": (_z, [_l, _l, _i]),
+    "tp3d_knn_workspace_bytes": (_z, [_i, _l, _i]),
+    "tp3d_voxel_workspace_bytes": (_z, [_l]),
+    "tp3d_ball_query_workspace_bytes": (_z, [_i, _l, _i]),
+}
 ABI_VERSION = 36
 
 _handle = None
@@ -105,50 +129,10 @@ def load():
         fn = getattr(h, name)  # AttributeError here = the .so does not match the header
         fn.argtypes = argtypes
         fn.restype = _i
-    h.tp3d_abi_version.restype = _i
-    h.tp3d_strerror.restype = ctypes.c_char_p
-    h.tp3d_strerror.argtypes = [_i]
-    h.tp3d_last_hip_error.restype = _i
-    h.tp3d_scatter_workspace_bytes.restype = ctypes.c_size_t
-    h.tp3d_scatter_workspace_bytes.argtypes = [_i, _i, _i, _i]
-    h.tp3d_bn_workspace_floats.restype = ctypes.c_size_t
-    h.tp3d_bn_workspace_floats.argtypes = [_l, _i]
-    h.tp3d_gemm_tn_workspace_floats.restype = ctypes.c_size_t
-    h.tp3d_gemm_tn_workspace_floats.argtypes = [_l, _i, _i]
-    h.tp3d_gemm_tn_x3_workspace_floats.restype = ctypes.c_size_t
-    h.tp3d_gemm_tn_x3_workspace_floats.argtypes = [_l, _i, _i]
-    h.tp3d_gemm_tn_x3_serves.restype = ctypes.c_int
-    h.tp3d_gemm_tn_x3_serves.argtypes = [_l, _i, _i]
-    h.tp3d_gemm_tn_x3_red_chunks.restype = ctypes.c_int
-    h.tp3d_gemm_tn_x3_red_chunks.argtypes = [_l, _i, _i]
-    h.tp3d_kpconv_bwd_workspace_bytes.restype = ctypes.c_size_t
-    h.tp3d_kpconv_bwd_workspace_bytes.argtypes = [_l, _l]
-    h.tp3d_gemm_rows_stat_floats.restype = ctypes.c_size_t
-    h.tp3d_gemm_rows_stat_floats.argtypes = [_l, _i]
-    h.tp3d_gemm_rows_stat_chunks.restype = ctypes.c_int
-    h.tp3d_gemm_rows_stat_chunks.argtypes = [_l, _i]
-    h.tp3d_gemm_rows_narrow_chunks.restype = ctypes.c_int
-    h.tp3d_gemm_rows_narrow_chunks.argtypes = [_l]
-    h.tp3d_gemm_tn_bn_narrow_serves.restype = ctypes.c_int
-    h.tp3d_gemm_tn_bn_narrow_serves.argtypes = [_l, _i, _i]
-    h.tp3d_gemm_tn_bn_narrow_workspace_floats.restype = ctypes.c_size_t
-    h.tp3d_gemm_tn_bn_narrow_workspace_floats.argtypes = [_l, _i, _i]
-    h.tp3d_gemm_rows_bnbwd_sp_serves.restype = ctypes.c_int
-    h.tp3d_gemm_rows_bnbwd_sp_serves.argtypes = [_l, _i, _i]
-    h.tp3d_gemm_rows_x3_chunks.restype = ctypes.c_int
-    h.tp3d_gemm_rows_x3_chunks.argtypes = [_l, _i, _i, _i]
-    h.tp3d_gemm_rows_sp_chunks.restype = ctypes.c_int
-    h.tp3d_gemm_rows_sp_chunks.argtypes = [_l, _i, _i, _i]
-    h.tp3d_gemm_rows_workspace_floats.restype = ctypes.c_size_t
-    h.tp3d_gemm_rows_workspace_floats.argtypes = [_l, _i, _i]
-    h.tp3d_kpconv_grad_workspace_bytes.restype = ctypes.c_size_t
-    h.tp3d_kpconv_grad_workspace_bytes.argtypes = [_l, _l, _i]
-    h.tp3d_knn_workspace_bytes.restype = ctypes.c_size_t
-    h.tp3d_knn_workspace_bytes.argtypes = [_i, _l, _i]
-    h.tp3d_voxel_workspace_bytes.restype = ctypes.c_size_t
-    h.tp3d_voxel_workspace_bytes.argtypes = [_l]
-    h.tp3d_ball_query_workspace_bytes.restype = ctypes.c_size_t
-    h.tp3d_ball_query_workspace_bytes.argtypes = [_i, _l, _i]
+    for name, (restype, argtypes) in MISC.items():
+        fn = getattr(h, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
     if h.tp3d_abi_version() != ABI_VERSION:
         raise Tp3dError("libtp3d_hip.so ABI %d != binding ABI %d" % (h.tp3d_abi_version(), ABI_VERSION))
     _handle = h
