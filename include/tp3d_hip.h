@@ -35,7 +35,7 @@ extern "C" {
 #define TP3D_E_UNSORTED (-3) /* reserved: batch vector not sorted (checked by the host wrapper) */
 #define TP3D_E_TOOBIG (-4)   /* size exceeds what the kernel's index arithmetic supports */
 
-#define TP3D_ABI_VERSION 36
+#define TP3D_ABI_VERSION 37
 
 int tp3d_abi_version(void);
 const char *tp3d_strerror(int code);
@@ -339,6 +339,41 @@ int tp3d_kpconv_bwd_features_f32(const float *query, const float *support, const
                                  int Cin, int KP, float extent, int influence, int closest, float *d_features,
                                  void *inverse, size_t inverse_bytes, int inverse_ready, void *workspace,
                                  size_t workspace_bytes, void *stream);
+
+/* KPConv deformable convolution, stage 1 (reference modules/KPConv/convolution_ops.py:110-235, KPConv_deform_ops).
+ * The rigid arguments plus offsets (Nq,KP,3) and modulations (Nq,KP) or NULL (= 1).  With
+ *   rel[q,n] = support[nbr[q,n]] - query[q]   (shadow neighbour: the point (1e6,1e6,1e6), zero features),
+ *   dk[q,k]  = k_points[k] + offsets[q,k],    d2[q,n,k] = |rel[q,n] - dk[q,k]|^2  ((dx*dx + dy*dy) + dz*dz, no fma),
+ *   in_range[q,n] = any_k d2[q,n,k] < extent^2   (extent^2 formed in double, rounded to fp32),
+ * it writes
+ *   weighted[q,k,:] = modulations[q,k] * sum_n in_range[q,n] * h(d2[q,n,k]) * features[nbr[q,n], :]      (Nq,KP,Cin)
+ *   kp_min_d2[q,k]  = min over ALL Mn slots of d2[q,n,k]  (or NULL), kp_argmin[q,k] its slot, first minimum (int32, or NULL;
+ *                     needs kp_min_d2) -- the only use the reference makes of its (Nq,Mn,KP) distances (losses.py:12).
+ * h: 0 constant (d2 < extent^2), 1 linear (max(1 - sqrt(d2)/extent, 0)), 2 gaussian (exp(-d2 / (2 (0.3 extent)^2 + 1e-9))).
+ * Sum aggregation only (the reference's deformable "closest" raises).  M, Mn >= 1, KP <= 16.  Mn <= 64 runs on the fp32
+ * matrix pipe, larger tables on the per-lane-FMA kernel.  Stage 2 is the same host GEMM as for the rigid convolution. */
+int tp3d_kpconv_deform_weighted_f32(const float *query, const float *support, const int64_t *neighbors,
+                                    const float *features, const float *k_points, const float *offsets,
+                                    const float *modulations, int64_t Nq, int64_t M, int Mn, int Cin, int KP, float extent,
+                                    int influence, float *weighted, float *kp_min_d2, int32_t *kp_argmin, void *stream);
+
+/* Backward of the deformable stage 1.  d_weighted (Nq,KP,Cin) = d_out @ W2^T (host GEMM; the gradient of the MODULATED
+ * weighted features), d_kp_min_d2 (Nq,KP) or NULL (then kp_argmin may be NULL), kp_argmin as the forward wrote it.
+ *   s[q,n,k]           = in_range[q,n] * sum_c features[nbr[q,n],c] * d_weighted[q,k,c]
+ *   d_offsets[q,k,:]   = sum_n modulations[q,k] * s[q,n,k] * dh/d dk  -  2 d_kp_min_d2[q,k] * (rel[q,argmin] - dk[q,k])
+ *   d_modulations[q,k] = sum_n s[q,n,k] * h(d2[q,n,k])                                     (NULL without modulations)
+ *   d_features[m,:]    = sum over (q,n) with nbr[q,n] == m of sum_k modulations * in_range * h * d_weighted[q,k,:]
+ *                        (NULL: not wanted; then inverse / workspace are not touched)
+ * No gradient flows through in_range, positions or k_points.  linear influence: the term of a pair with d2 == 0 (the
+ * reference: NaN) and of a pair at or beyond the extent is 0.  All outputs are overwritten; atomic-free, fixed
+ * summation order.  inverse / inverse_ready / workspace: exactly as for tp3d_kpconv_bwd_features_f32
+ * (tp3d_kpconv_bwd_workspace_bytes, tp3d_kpconv_grad_workspace_bytes); the inverted table is shared with it. */
+int tp3d_kpconv_deform_bwd_f32(const float *query, const float *support, const int64_t *neighbors, const float *features,
+                               const float *k_points, const float *offsets, const float *modulations,
+                               const float *d_weighted, const float *d_kp_min_d2, const int32_t *kp_argmin, int64_t Nq,
+                               int64_t M, int Mn, int Cin, int KP, float extent, int influence, float *d_features,
+                               float *d_offsets, float *d_modulations, void *inverse, size_t inverse_bytes,
+                               int inverse_ready, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Geometric relation rows of Relation-Shape convolution (reference modules/RSConv/dense.py:86-101):
  *   out[(b,j,s), 0:10] = [ |d|, new_pos[b,j] (3), p (3), d (3) ],  p = pos[b, idx[b,j,s]],  d = p - new_pos[b,j];

@@ -3,7 +3,10 @@
 (in_feat 64, in_grid_size 0.02, 25 neighbours).  Prints ms per forward (and forward+backward with --train) plus the
 per-entry-point device time of the library calls.
 
-    python tools/bench_kpconv.py [--n 65536] [--iters 20] [--train] [--clouds 1]
+    python tools/bench_kpconv.py [--n 65536] [--iters 20] [--train] [--clouds 1] [--deformable]
+
+--deformable: the second block of levels 2-4 is deformable, as in the reference's KPDeformableConvPaper
+(conf/models/segmentation/kpconv.yaml:78-149); with --train the internal losses are added to the objective.
 """
 import argparse
 import json
@@ -41,6 +44,7 @@ def main():
                     help="sampling / neighbour search / interpolation tables computed once by MultiScaleTransform "
                          "(the reference's data-loader precompute, on the device); the timed forward only convolves")
     ap.add_argument("--graph", action="store_true", help="with --precomputed: replay the forward from one HIP graph")
+    ap.add_argument("--deformable", action="store_true", help="deformable second block at levels 2-4")
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE",
                     help="experiment switch: an attribute of torch_points3d_amd.fused (as bench.py --set)")
     args = ap.parse_args()
@@ -49,10 +53,17 @@ def main():
         name, val = kv.split("=")
         setattr(fused, name, type(getattr(fused, name))(int(val)))
     from torch_points3d_amd.kpconv_blocks import PDData
-    from torch_points3d_amd.kpconv_unet import KPConv
+    from torch_points3d_amd.kpconv_losses import internal_loss
+    from torch_points3d_amd.kpconv_unet import KPConv, unet_config
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    model = KPConv("unet", input_nc=3, in_feat=args.in_feat, in_grid_size=0.02, num_layers=4, output_nc=13).to(dev)
+    config = None
+    if args.deformable:
+        config = unet_config(4, 3, args.in_feat, 0.02)
+        for level in config["down_conv"][2:]:
+            level["deformable"] = [False, True]
+    model = KPConv("unet", input_nc=3, in_feat=args.in_feat, in_grid_size=0.02, num_layers=4, output_nc=13,
+                   config=config).to(dev)
     pos, batch = synthetic_cloud(args.n, args.clouds, 0.02)
     x = torch.cat([torch.ones(pos.shape[0], 1), torch.randn(pos.shape[0], 3)], 1)
     pos, batch, x = pos.to(dev), batch.to(dev), x.to(dev)
@@ -76,7 +87,7 @@ def main():
             data.multiscale, data.upsample = tables.multiscale, tables.upsample
         if args.train:
             out = model(data)
-            out.x.square().mean().backward()
+            (out.x.square().mean() + (0.1 * internal_loss(model) if args.deformable else 0.0)).backward()
             for p in model.parameters():
                 p.grad = None
         else:
@@ -100,7 +111,7 @@ def main():
         def loss_fn():
             data = PDData(pos=pos, batch=batch, x=x)
             data.multiscale, data.upsample = tables.multiscale, tables.upsample
-            return model(data).x.square().mean()
+            return model(data).x.square().mean() + (0.1 * internal_loss(model) if args.deformable else 0.0)
         trainer = ShardedStep(model, lambda ps: torch.optim.Adam(ps, lr=1e-3, capturable=True), loss_fn, use_graph=True,
                               log=lambda m: print("[bench_kpconv] " + m, file=sys.stderr))
         if not trainer.warmup_and_capture(3):
@@ -142,6 +153,8 @@ def main():
     top = sorted(per_entry.items(), key=lambda kv: -kv[1][1])
     mode = ("train" if args.train else "forward") + ("_precomputed" if args.precomputed else "") + \
            ("_graph" if args.graph else "")
+    if args.deformable:
+        mode += "_deformable"
     print(json.dumps({"workload": "kpconv_unet4_%s" % mode, "precompute_ms": None if pre_ms is None else round(pre_ms, 3),
                       "points": pos.shape[0],
                       "clouds": args.clouds, "in_feat": args.in_feat, "ms": round(ms, 3),

@@ -61,6 +61,9 @@ SIGNATURES = {
     "tp3d_cluster_mean_f32": [_p, _p, _p, _l, _i, _p, _p],
     "tp3d_cluster_majority_i64": [_p, _p, _p, _l, _l, _l, _p, _p],
     "tp3d_kpconv_weighted_f32": [_p, _p, _p, _p, _p, _l, _l, _i, _i, _i, _f, _i, _i, _p, _p],
+    "tp3d_kpconv_deform_weighted_f32": [_p, _p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _i, _f, _i, _p, _p, _p, _p],
+    "tp3d_kpconv_deform_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _i, _f, _i, _p, _p, _p, _p,
+                                   ctypes.c_size_t, _i, _p, ctypes.c_size_t, _p],
     "tp3d_gemm_skinny_f32": [_p, _p, _l, _i, _i, _i, _p, _p],
     "tp3d_gemm_skinny_bnact_f32": [_p, _p, _l, _i, _i, _i, _p, _p, _p, _f, _p, _p],
     "tp3d_randla_relpos_f32": [_p, _p, _p, _l, _i, _l, _p, _p],
@@ -101,7 +104,7 @@ MISC = {
     "tp3d_voxel_workspace_bytes": (_z, [_l]),
     "tp3d_ball_query_workspace_bytes": (_z, [_i, _l, _i]),
 }
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 _handle = None
 

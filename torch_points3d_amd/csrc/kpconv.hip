@@ -502,8 +502,8 @@ int invert_table(const int64_t *idx, int64_t slots, int64_t M, int *cnt, int *st
 }
 
 // workspace: tp3d_kpconv_bwd_workspace_bytes(M, slots)
-static int invert_neighbors(const int64_t *neighbors, int64_t slots, int64_t M, void *workspace, int **start_out,
-                            int **order_out, hipStream_t s, bool ready = false)
+int invert_neighbors(const int64_t *neighbors, int64_t slots, int64_t M, void *workspace, int **start_out,
+                     int **order_out, hipStream_t s, bool ready)
 {
     auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     char *p = static_cast<char *>(workspace);
@@ -663,6 +663,14 @@ __global__ __launch_bounds__(KP_BLOCK) void kpconv_bwd_gather_kernel(const float
     }
 }
 
+// d_x[m, :] = sum of the per-slot rows g that reference m (shared with the deformable backward, kpconv_deform.hip)
+int gather_slot_rows(const float *g, const int *start, const int *order, int64_t M, int Cin, float *d_x, hipStream_t s)
+{
+    hipLaunchKernelGGL(kpconv_bwd_gather_kernel, dim3((unsigned)((M + KP_BLOCK / 64 - 1) / (KP_BLOCK / 64))),
+                       dim3(KP_BLOCK), 0, s, g, start, order, M, Cin, d_x);
+    return check_launch();
+}
+
 }  // namespace tp3d
 
 TP3D_EXPORT size_t tp3d_kpconv_bwd_workspace_bytes(int64_t M, int64_t slots)
@@ -705,9 +713,7 @@ TP3D_EXPORT int tp3d_kpconv_bwd_features_f32(const float *query, const float *su
     else
         hipLaunchKernelGGL(kpconv_bwd_slots_kernel<false>, qgrid, dim3(KP_BLOCK), 0, s, query, support, neighbors, k_points,
                            d_weighted, Nq, M, Mn, Cin, KP, extent, influence, g);
-    hipLaunchKernelGGL(kpconv_bwd_gather_kernel, dim3((unsigned)((M + KP_BLOCK / 64 - 1) / (KP_BLOCK / 64))),
-                       dim3(KP_BLOCK), 0, s, g, start, order, M, Cin, d_features);
-    return check_launch();
+    return gather_slot_rows(g, start, order, M, Cin, d_features, s);
 }
 
 TP3D_EXPORT int tp3d_nbr_maxpool_fwd_f32(const float *x, const int64_t *neighbors, int64_t Nq, int64_t M, int Mn, int C,

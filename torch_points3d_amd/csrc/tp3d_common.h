@@ -78,6 +78,11 @@ int gather_sum(const float *rows, const int *start, const int *order, const floa
 // per_cloud_bins + value, M = clouds * per_cloud_bins (one flat table over the batch).
 int invert_table(const int64_t *idx, int64_t slots, int64_t M, int *cnt, int *start, int *cursor, int *order,
                  hipStream_t s, int64_t per_cloud_slots = 0, int64_t per_cloud_bins = 0, int *merge_tmp = nullptr);
+// kpconv.hip: the inverted neighbour table inside a tp3d_kpconv_bwd_workspace_bytes(M, slots) buffer (built unless
+// `ready`), and the per-support-point sum of per-slot gradient rows through it (ascending slot order)
+int invert_neighbors(const int64_t *neighbors, int64_t slots, int64_t M, void *workspace, int **start_out,
+                     int **order_out, hipStream_t s, bool ready = false);
+int gather_slot_rows(const float *g, const int *start, const int *order, int64_t M, int Cin, float *d_x, hipStream_t s);
 // csr.hip: does the one-workgroup-per-cloud transpose fit LDS?
 bool csr_fits_lds(int L, int nbins);
 

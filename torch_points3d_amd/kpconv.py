@@ -7,6 +7,10 @@ neighbourhood features) and its backward are HIP kernels (csrc/kpconv.hip); stag
 (Nq, KP*Cin) x (KP*Cin, Cout) GEMM the reference's permute/matmul/sum amounts to; the kernel-weight gradient runs
 on the split-K MFMA kernel (csrc/gemm_tn.hip).  Differentiable wrt `features` and `K_values` (what the reference
 trains); positions and kernel points carry no gradient (kernels.py:57-59 sets requires_grad=False on K_points).
+
+The deformable convolution (`KPConv_deform_ops`, convolution_ops.py:110-235; `KPConvDeformableLayer`,
+kernels.py:107-256) runs on csrc/kpconv_deform.hip: per-query kernel points, in-range mask, modulations and the
+fitting-loss distances in the forward kernel; gradients wrt features, offsets and modulations in one backward kernel.
 """
 import torch
 import torch.nn as nn
@@ -77,6 +81,107 @@ def KPConv_ops(query_points, support_points, neighbors_indices, features, K_poin
                          int(aggregation_mode == "closest"))
 
 
+class _KPConvDeform(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, K_values, offsets, modulations, query, support, nbr, kp, extent, influence):
+        dev = query.device
+        x = features.detach().float().contiguous()
+        W = K_values.detach().float().contiguous()
+        off = offsets.detach().float().contiguous()
+        mod = None if modulations is None else modulations.detach().float().contiguous()
+        Nq, Mn = nbr.shape
+        M, Cin = x.shape
+        KP = kp.shape[0]
+        wf = torch.empty((Nq, KP * Cin), dtype=torch.float32, device=dev)
+        kp_min = torch.empty((Nq, KP), dtype=torch.float32, device=dev)
+        kp_arg = torch.empty((Nq, KP), dtype=torch.int32, device=dev)
+        with _lib.on_device(dev):
+            _lib.call("tp3d_kpconv_deform_weighted_f32", _lib.ptr(query), _lib.ptr(support), _lib.ptr(nbr), _lib.ptr(x),
+                      _lib.ptr(kp), _lib.ptr(off), _lib.ptr(mod), Nq, M, Mn, Cin, KP, float(extent), influence,
+                      _lib.ptr(wf), _lib.ptr(kp_min), _lib.ptr(kp_arg), _lib.stream_ptr(dev))
+        out = torch.mm(wf, W.reshape(KP * Cin, -1))
+        ctx.save_for_backward(query, support, nbr, kp, x, W, off, mod, wf, kp_arg)
+        ctx.cfg = (float(extent), influence, M, Cin, KP, tuple(K_values.shape))
+        return out, kp_min
+
+    @staticmethod
+    def backward(ctx, d_out, d_kp_min):
+        query, support, nbr, kp, x, W, off, mod, wf, kp_arg = ctx.saved_tensors
+        extent, influence, M, Cin, KP, wshape = ctx.cfg
+        dev = d_out.device
+        d_out = d_out.float().contiguous()
+        Nq, Mn = nbr.shape
+        need = ctx.needs_input_grad
+        dW = gemm_tn(wf, d_out).reshape(wshape) if need[1] else None
+        dx = d_off = d_mod = None
+        if need[0] or need[2] or need[3]:
+            d_wf = torch.mm(d_out, W.reshape(KP * Cin, -1).t())  # (Nq, KP*Cin)
+            d_kp_min = None if d_kp_min is None else d_kp_min.float().contiguous()
+            d_off = torch.empty((Nq, KP, 3), dtype=torch.float32, device=dev)
+            d_mod = torch.empty((Nq, KP), dtype=torch.float32, device=dev) if mod is not None else None
+            inv = ws = None
+            inv_bytes = nbytes = ready = 0
+            token = None
+            with _lib.on_device(dev):
+                if need[0]:
+                    dx = torch.empty((M, Cin), dtype=torch.float32, device=dev)
+                    nbytes = _lib.load().tp3d_kpconv_grad_workspace_bytes(M, Nq * Mn, Cin)
+                    ws = _lib.workspace("kpconv_bwd", nbytes, dev)
+                    inv, inv_bytes, ready, token = _lib.neighbour_inverse(nbr, M, dev)
+                _lib.call("tp3d_kpconv_deform_bwd_f32", _lib.ptr(query), _lib.ptr(support), _lib.ptr(nbr), _lib.ptr(x),
+                          _lib.ptr(kp), _lib.ptr(off), _lib.ptr(mod), _lib.ptr(d_wf), _lib.ptr(d_kp_min), _lib.ptr(kp_arg),
+                          Nq, M, Mn, Cin, KP, extent, influence, _lib.ptr(dx), _lib.ptr(d_off), _lib.ptr(d_mod),
+                          _lib.ptr(inv), inv_bytes, ready, _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+                _lib.inverse_built(token, dev)
+            if not need[2]:
+                d_off = None
+            if not need[3]:
+                d_mod = None
+        return dx, dW, d_off, d_mod, None, None, None, None, None, None
+
+
+def KPConv_deform_ops(query_points, support_points, neighbors_indices, features, K_points, offsets, modulations, K_values,
+                      KP_extent, KP_influence, aggregation_mode):
+    """Deformable kernel-point convolution with the reference's argument list (convolution_ops.py:110-235):
+    offsets (Nq, KP, 3) move the kernel points of every query, a neighbour in range (`KP_extent`) of no deformed kernel
+    point contributes nothing, `modulations` (Nq, KP) or None scale the weighted features.
+
+    Returns `(features (Nq, Cout), kp_min_d2 (Nq, KP), deformed_K_points (Nq, KP, 3))`.  ONE deviation from the
+    reference's triple: its second item is the whole (Nq, Mn, KP) tensor of squared distances, whose only consumer is
+    `fitting_loss`, which takes the minimum over the neighbours first (losses.py:12); here that minimum (over all Mn
+    slots, a shadow neighbour being the point (1e6, 1e6, 1e6)) is what the kernel returns, and
+    `kpconv_losses.fitting_loss` accepts either form.
+
+    Differentiable wrt `features`, `K_values`, `offsets` and `modulations`; a gradient arriving on `kp_min_d2` flows to
+    `offsets` through the arg-min slot, one arriving on `deformed_K_points` through the plain addition.  No gradient
+    through the in-range mask, the positions or `K_points`.  With linear influence the reference yields NaN for a
+    pair at distance exactly 0 (backward of sqrt at 0 times 0); that term is defined as 0 here.
+    `aggregation_mode="closest"` is not a valid call in the reference either (its argmin raises TypeError)."""
+    if KP_influence not in _INFLUENCE:
+        raise ValueError("Unknown influence function type (config.KP_influence)")
+    if aggregation_mode == "closest":
+        raise NotImplementedError("KPConv_deform_ops: aggregation_mode='closest' is not defined for the deformable "
+                                  "convolution (the reference raises on it as well); use 'sum'")
+    if aggregation_mode != "sum":
+        raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
+    tensors = [query_points, support_points, neighbors_indices, features, K_points, offsets, K_values]
+    if modulations is not None:
+        tensors.append(modulations)
+    for t in tensors:
+        if t.device.type != "cuda":
+            raise RuntimeError("torch_points3d_amd runs on MI355X only: got a %s tensor (no CPU fallback is provided)"
+                               % t.device.type)
+    if support_points.shape[0] == 0 or neighbors_indices.shape[1] == 0:
+        raise ValueError("KPConv_deform_ops needs at least one support point and one neighbour slot")
+    q = query_points.detach().float().contiguous()
+    s = support_points.detach().float().contiguous()
+    nbr = neighbors_indices.long().contiguous()
+    kp = K_points.detach().float().contiguous()
+    out, kp_min_d2 = _KPConvDeform.apply(features, K_values, offsets, modulations, q, s, nbr, kp, float(KP_extent),
+                                         _INFLUENCE[KP_influence])
+    return out, kp_min_d2, offsets + kp
+
+
 def default_kernel_points(num_points=15, iterations=400):
     """A kernel-point disposition in unit scale: one point at the centre, the others spread over the unit sphere by
     electrostatic repulsion from a Fibonacci lattice (deterministic).
@@ -132,3 +237,79 @@ class KPConvLayer(nn.Module):
             x = ones if x is None else torch.cat([ones, x.float()], dim=-1)
         return KPConv_ops(query_points, support_points, neighbors, x, self.K_points, self.weight, self.point_influence,
                           self.KP_influence, self.aggregation_mode)
+
+
+class KPConvDeformableLayer(nn.Module):
+    """Deformable kernel-point convolution layer with the reference's parameters and forward
+    (modules/KPConv/kernels.py:107-256): `K_points` frozen, `offset_weights` (KP, Cin, 3 KP or 4 KP when `modulated`)
+    xavier-normal, `offset_bias` zeros, `weight` (KP, Cin, Cout).  A rigid convolution with `offset_weights` predicts
+    per-query offsets (in units of `point_influence`) and, when `modulated`, 2 * sigmoid modulations; the deformable
+    convolution then runs with them.  The regularisers of the pass are left in `internal_losses`
+    (`get_internal_losses()`): fitting + repulsion with `loss_mode="fitting"`, permissive with "permissive".
+    `K_points` (KP, 3) is passed in, as for `KPConvLayer`."""
+
+    PERMISSIVE_LOSS_KEY = "permissive_loss"
+    FITTING_LOSS_KEY = "fitting_loss"
+    REPULSION_LOSS_KEY = "repulsion_loss"
+
+    _INFLUENCE_TO_RADIUS = 1.5
+
+    def __init__(self, num_inputs, num_outputs, point_influence, K_points, KP_influence="linear", aggregation_mode="sum",
+                 modulated=False, loss_mode="fitting", add_one=False, **kwargs):
+        # **kwargs: n_kernel_points / fixed / dimension of the reference's YAML are implied by K_points here
+        super().__init__()
+        self.kernel_radius = self._INFLUENCE_TO_RADIUS * point_influence
+        self.point_influence = point_influence
+        self.add_one = add_one
+        self.num_inputs = num_inputs + int(add_one)
+        self.num_outputs = num_outputs
+        self.KP_influence = KP_influence
+        self.aggregation_mode = aggregation_mode
+        self.modulated = modulated
+        self.internal_losses = {self.PERMISSIVE_LOSS_KEY: 0.0, self.FITTING_LOSS_KEY: 0.0, self.REPULSION_LOSS_KEY: 0.0}
+        self.loss_mode = loss_mode
+        K_points = torch.as_tensor(K_points, dtype=torch.float32)
+        self.n_kernel_points = K_points.shape[0]
+        self.K_points = nn.Parameter(K_points.clone(), requires_grad=False)
+        offset_dim = (4 if modulated else 3) * self.n_kernel_points
+        offset_weights = torch.empty([self.n_kernel_points, self.num_inputs, offset_dim], dtype=torch.float32)
+        nn.init.xavier_normal_(offset_weights)
+        self.offset_weights = nn.Parameter(offset_weights)
+        self.offset_bias = nn.Parameter(torch.zeros(offset_dim, dtype=torch.float32))
+        w = torch.empty([self.n_kernel_points, self.num_inputs, num_outputs], dtype=torch.float32)
+        nn.init.xavier_normal_(w)
+        self.weight = nn.Parameter(w)
+
+    def forward(self, query_points, support_points, neighbors, x):
+        from . import kpconv_losses as _losses
+        if self.add_one:
+            ones = torch.ones(support_points.shape[0], 1, dtype=torch.float32, device=support_points.device)
+            x = ones if x is None else torch.cat([ones, x.float()], dim=-1)
+        offset_feat = KPConv_ops(query_points, support_points, neighbors, x, self.K_points, self.offset_weights,
+                                 self.point_influence, self.KP_influence, self.aggregation_mode) + self.offset_bias
+        KP = self.n_kernel_points
+        if self.modulated:
+            offsets = offset_feat[:, :3 * KP].reshape(-1, KP, 3)
+            modulations = 2 * torch.sigmoid(offset_feat[:, 3 * KP:])
+        else:
+            offsets = offset_feat.reshape(-1, KP, 3)
+            modulations = None
+        offsets = offsets * self.point_influence
+        new_feat, kp_min_d2, K_points_deformed = KPConv_deform_ops(
+            query_points, support_points, neighbors, x, self.K_points, offsets, modulations, self.weight,
+            self.point_influence, self.KP_influence, self.aggregation_mode)
+        if self.loss_mode == "fitting":
+            self.internal_losses[self.FITTING_LOSS_KEY] = _losses.fitting_loss(kp_min_d2, self.kernel_radius)
+            self.internal_losses[self.REPULSION_LOSS_KEY] = _losses.repulsion_loss(K_points_deformed, self.point_influence)
+        elif self.loss_mode == "permissive":
+            self.internal_losses[self.PERMISSIVE_LOSS_KEY] = _losses.permissive_loss(K_points_deformed, self.kernel_radius)
+        else:
+            raise NotImplementedError("Loss mode %s not recognised. Only permissive and fitting are valid" % self.loss_mode)
+        return new_feat
+
+    def get_internal_losses(self):
+        return self.internal_losses
+
+    def __repr__(self):
+        return "KPConvDeformableLayer(InF: %i, OutF: %i, kernel_pts: %i, radius: %.2f, KP_influence: %s)" % (
+            self.num_inputs, self.num_outputs, self.n_kernel_points, self.kernel_radius, self.KP_influence)

@@ -26,7 +26,7 @@ import torch.nn as nn
 from . import fused as _fused
 from . import torchpoints as _tp
 from .grid_sampling import GridSampling3D
-from .kpconv import KPConvLayer, default_kernel_points
+from .kpconv import KPConvDeformableLayer, KPConvLayer, default_kernel_points
 
 
 class PDData(object):
@@ -97,13 +97,16 @@ class RadiusNeighbourFinder(object):
 
 
 class SimpleBlock(nn.Module):
-    """KPConv -> BatchNorm -> LeakyReLU(0.1); strided when prev_grid_size != grid_size."""
+    """KPConv -> BatchNorm -> LeakyReLU(0.1); strided when prev_grid_size != grid_size.  deformable=True builds a
+    `KPConvDeformableLayer` and searches with the wider radius of the reference (5.0 * sigma * prev_grid_size,
+    blocks.py:22,42-52); `modulated` / `loss_mode` reach it through **kwargs."""
 
+    DEFORMABLE_DENSITY = 5.0
     RIGID_DENSITY = 2.5
 
     def __init__(self, down_conv_nn=None, grid_size=None, prev_grid_size=None, sigma=1.0, max_num_neighbors=16,
-                 activation=None, bn_momentum=0.02, bn=FastBatchNorm1d, add_one=False, kernel_points=None, sampler=None,
-                 fused=True, **kwargs):
+                 activation=None, bn_momentum=0.02, bn=FastBatchNorm1d, deformable=False, add_one=False, kernel_points=None,
+                 sampler=None, fused=True, **kwargs):
         super().__init__()
         assert len(down_conv_nn) == 2
         self.fused = fused
@@ -112,9 +115,10 @@ class SimpleBlock(nn.Module):
         num_inputs, num_outputs = down_conv_nn
         influence = prev_grid_size * sigma
         kp = torch.as_tensor(kernel_points, dtype=torch.float32) * (KPConvLayer._INFLUENCE_TO_RADIUS * influence)
-        self.kp_conv = KPConvLayer(num_inputs, num_outputs, point_influence=influence, K_points=kp, add_one=add_one,
-                                   **kwargs)
-        self.neighbour_finder = RadiusNeighbourFinder(self.RIGID_DENSITY * sigma * prev_grid_size, max_num_neighbors)
+        layer = KPConvDeformableLayer if deformable else KPConvLayer
+        self.kp_conv = layer(num_inputs, num_outputs, point_influence=influence, K_points=kp, add_one=add_one, **kwargs)
+        density = self.DEFORMABLE_DENSITY if deformable else self.RIGID_DENSITY
+        self.neighbour_finder = RadiusNeighbourFinder(density * sigma * prev_grid_size, max_num_neighbors)
         self.bn = bn(num_outputs, momentum=bn_momentum) if bn else None
         self.activation = activation if activation is not None else nn.LeakyReLU(negative_slope=0.1)
         self.is_strided = prev_grid_size != grid_size
