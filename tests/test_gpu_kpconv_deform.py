@@ -151,7 +151,7 @@ def _hip_op(q, s, nbr, f, kp, o, m, w, extent, influence):
 
 SHAPES = [(5000, 6000, 25, 64, 128), (3000, 3000, 38, 1, 64), (700, 900, 60, 130, 70), (1, 4, 3, 5, 2),
           (65536, 65536, 25, 16, 32), (300, 400, 70, 8, 4), (900, 1000, 20, 64, 24), (900, 1000, 35, 130, 16),
-          (900, 1000, 45, 1, 8), (600, 800, 70, 64, 8), (900, 1000, 30, 2, 2)]
+          (900, 1000, 45, 1, 8), (600, 800, 70, 64, 8), (900, 1000, 30, 2, 2), (4200, 4300, 25, 130, 8)]
 
 
 @pytest.mark.parametrize("influence,use_mod", [("linear", True), ("gaussian", False), ("constant", True)])

@@ -15,79 +15,29 @@
 // in-range mask of a neighbour is a ballot over its 16 kernel-point lanes, and the backward contracts features with
 // d_wf on the matrix pipe (channels are the contraction index) to get the (kernel point, neighbour) sensitivities
 // the offset and modulation gradients are made of.  No atomics; every sum has a fixed order.
-#include <algorithm>
-
-#include "tp3d_common.h"
+// The per-query pieces shared with the rigid convolution are in kp_common.h.
+#include "kp_common.h"
 
 namespace tp3d {
 
-typedef float kd_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int KD_BLOCK = 256;   // 4 waves, one query per wave
-constexpr int KD_MAX = 16;      // kernel points
-constexpr int KD_NMAX = 64;     // neighbours per matrix-pipe pass (one lane each when they are fetched)
-constexpr int KD_CB = 4;        // 16-channel blocks accumulated together in the forward
-constexpr int KD_NCH = 48;      // neighbours per LDS pass of the per-lane-FMA forward
-constexpr int KD_GROUP = 16;    // neighbour rows fetched together there
-constexpr int KD_WPAD = 17;     // row stride of the backward's weight tile (conflict-free column reads)
+constexpr int KD_WPAD = 17;          // row stride of the backward's weight tile (conflict-free column reads)
 constexpr float KD_SHADOW = 1.0e6f;  // convolution_ops.py:146
 
-// the wave's own LDS writes have landed (every wave owns its slice: no workgroup barrier anywhere in this file)
-__device__ __forceinline__ void kd_lds_sync()
+// a shadow neighbour of query q sits at (1e6, 1e6, 1e6) and takes part in kp_min: its centred position
+__device__ __forceinline__ float4 kd_shadow_rel(float qx, float qy, float qz)
 {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    return make_float4(KD_SHADOW - qx, KD_SHADOW - qy, KD_SHADOW - qz, 0.0f);
 }
 
-struct KdInfluence {
-    float ext2, inv_extent, gden;
-    int mode;
-};
-
-__device__ __forceinline__ KdInfluence kd_influence(float extent, float ext2, int mode)
-{
-    const float sigma = extent * 0.3f;
-    return KdInfluence{ext2, 1.0f / extent, 2.0f * sigma * sigma + 1e-9f, mode};
-}
-
-__device__ __forceinline__ float kd_h(float d2, const KdInfluence &f)
-{
-    if (f.mode == 0) return d2 < f.ext2 ? 1.0f : 0.0f;
-    if (f.mode == 1) return fmaxf(1.0f - __builtin_amdgcn_sqrtf(d2) * f.inv_extent, 0.0f);
-    return expf(-d2 / f.gden);
-}
+// the deformable constant influence is cut at the extent (tests/kpconv_deform_ref.py)
+__device__ __forceinline__ float kd_h(float d2, const KpInfluence &f) { return kp_h<true>(d2, f); }
 
 // g with  d h / d dk = g * (rel - dk);  linear at d2 == 0 (the reference: NaN) and at the clamp: 0
-__device__ __forceinline__ float kd_dh(float d2, float h, const KdInfluence &f)
+__device__ __forceinline__ float kd_dh(float d2, float h, const KpInfluence &f)
 {
     if (f.mode == 1) return (h > 0.0f && d2 > 0.0f) ? f.inv_extent / __builtin_amdgcn_sqrtf(d2) : 0.0f;
     if (f.mode == 2) return h * (2.0f / f.gden);
     return 0.0f;
-}
-
-// lane n of a chunk of `cnt` <= 64 neighbours: its id (-1 = shadow) and centred position into the wave's LDS slice;
-// a shadow neighbour sits at (1e6, 1e6, 1e6), lanes in [cnt, fill) get id -1 and a zero position (they are masked out)
-__device__ __forceinline__ void kd_fetch_neighbours(const float *__restrict__ support, const int64_t *__restrict__ nbr_row,
-                                                    int cnt, int fill, int64_t M, float qx, float qy, float qz,
-                                                    float4 *rel, int *ids, int lane)
-{
-    if (lane < fill) {
-        const int64_t id = lane < cnt ? nbr_row[lane] : -1;
-        const bool shadow = id < 0 || id >= M;
-        float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (!shadow) {
-            r.x = support[id * 3 + 0] - qx;
-            r.y = support[id * 3 + 1] - qy;
-            r.z = support[id * 3 + 2] - qz;
-        } else if (lane < cnt) {
-            r.x = KD_SHADOW - qx;
-            r.y = KD_SHADOW - qy;
-            r.z = KD_SHADOW - qz;
-        }
-        ids[lane] = shadow ? -1 : (int)id;
-        rel[lane] = r;
-    }
 }
 
 // first minimum over the four neighbour groups of a kernel-point lane (lanes k, k + 16, k + 32, k + 48)
@@ -106,25 +56,25 @@ __device__ __forceinline__ void kd_reduce_min(float &best, int &barg)
 
 // ------------------------------------------------------------------------------------------------ forward, matrix pipe
 template <int SMAX>  // most MFMA steps of four neighbours: 8 (Mn <= 32) or 16 (Mn <= 64)
-__global__ __launch_bounds__(KD_BLOCK) void kpconv_deform_mfma_kernel(
+__global__ __launch_bounds__(KP_BLOCK) void kpconv_deform_mfma_kernel(
     const float *__restrict__ query, const float *__restrict__ support, const int64_t *__restrict__ nbr,
     const float *__restrict__ feat, const float *__restrict__ kpts, const float *__restrict__ offsets,
     const float *__restrict__ mods, int64_t Nq, int64_t M, int Mn, int Cin, int KP, float extent, float ext2,
     int influence, int cpass, float *__restrict__ wf, float *__restrict__ kp_min, int *__restrict__ kp_arg)
 {
-    __shared__ __attribute__((aligned(16))) float4 s_rel[KD_BLOCK / 64][KD_NMAX];
-    __shared__ int s_id[KD_BLOCK / 64][KD_NMAX];
+    __shared__ __attribute__((aligned(16))) float4 s_rel[KP_BLOCK / 64][KP_NMAX];
+    __shared__ int s_id[KP_BLOCK / 64][KP_NMAX];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t q = (int64_t)blockIdx.x * (KD_BLOCK / 64) + wave;
+    const int64_t q = (int64_t)blockIdx.x * (KP_BLOCK / 64) + wave;
     if (q >= Nq) return;  // wave-uniform
     float4 *rel = s_rel[wave];
     int *ids = s_id[wave];
     const float qx = query[q * 3 + 0], qy = query[q * 3 + 1], qz = query[q * 3 + 2];
-    const KdInfluence infl = kd_influence(extent, ext2, influence);
+    const KpInfluence infl = kp_influence(extent, influence, ext2);
     const int steps = (Mn + 3) / 4;
-    kd_fetch_neighbours(support, nbr + q * Mn, Mn, 64, M, qx, qy, qz, rel, ids, lane);
-    kd_lds_sync();
-    const int k = lane & 15, nsub = lane >> 4, c16 = lane & 15;
+    kp_fetch_neighbours(support, nbr + q * Mn, Mn, 64, M, qx, qy, qz, kd_shadow_rel(qx, qy, qz), rel, ids, lane);
+    wave_lds_sync();
+    const int k = lane & 15, nsub = lane >> 4;
     const bool kreal = k < KP;
     float kx = 0.0f, ky = 0.0f, kz = 0.0f;
     if (kreal) {  // this query's own kernel point: K_k + offset (torch.add(offsets, K_points), convolution_ops.py:156)
@@ -169,68 +119,29 @@ __global__ __launch_bounds__(KD_BLOCK) void kpconv_deform_mfma_kernel(
     float modv[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) modv[j] = mods ? mods[q * KP + min(4 * nsub + j, KP - 1)] : 1.0f;
-    float *__restrict__ wq = wf + (size_t)q * KP * Cin;
-    const int c_lo = (int)blockIdx.y * cpass, c_hi = min(Cin, c_lo + cpass);
-    for (int c0 = c_lo; c0 < c_hi; c0 += 16 * KD_CB) {
-        const int nblk = min(KD_CB, (c_hi - c0 + 15) / 16);  // (wave-uniform)
-        kd_f32x4 acc[KD_CB];
-#pragma unroll
-        for (int b = 0; b < KD_CB; ++b) acc[b] = (kd_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-        const float *__restrict__ fb = feat + c0;
-        unsigned coff[KD_CB];  // this lane's channel inside the pass, clamped to the row
-#pragma unroll
-        for (int b = 0; b < KD_CB; ++b) coff[b] = (unsigned)min(16 * b + c16, Cin - 1 - c0);
-#pragma unroll
-        for (int s0 = 0; s0 < SMAX; s0 += 4) {
-            if (s0 < steps) {
-                float v[4][KD_CB];
-#pragma unroll
-                for (int b = 0; b < KD_CB; ++b)
-                    if (b < nblk) {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) v[u][b] = fb[roff[s0 + u] + coff[b]];
-                    }
-#pragma unroll
-                for (int b = 0; b < KD_CB; ++b)
-                    if (b < nblk) {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u)
-                            acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s0 + u], v[u][b], acc[b], 0, 0, 0);
-                    }
-            }
-        }
-        // D[kernel point = 4 (lane >> 4) + j][channel = lane & 15], modulated on the way out
-#pragma unroll
-        for (int b = 0; b < KD_CB; ++b)
-            if (b < nblk) {
-                const int c = c0 + 16 * b + c16;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int kp = 4 * nsub + j;
-                    if (kp < KP && c < Cin) wq[(unsigned)(kp * Cin + c)] = acc[b][j] * modv[j];
-                }
-            }
-    }
+    // gather the rows and accumulate on the matrix pipe, this grid row's channels, modulated on the way out
+    const int c_lo = (int)blockIdx.y * cpass;
+    kp_mfma_contract<SMAX>(feat, a, roff, steps, c_lo, min(Cin, c_lo + cpass), Cin, KP, lane, wf + (size_t)q * KP * Cin, modv);
 }
 
 // ------------------------------------------------------------------------------------- forward, per-lane FMA (any Mn)
-__global__ __launch_bounds__(KD_BLOCK) void kpconv_deform_fma_kernel(
+__global__ __launch_bounds__(KP_BLOCK) void kpconv_deform_fma_kernel(
     const float *__restrict__ query, const float *__restrict__ support, const int64_t *__restrict__ nbr,
     const float *__restrict__ feat, const float *__restrict__ kpts, const float *__restrict__ offsets,
     const float *__restrict__ mods, int64_t Nq, int64_t M, int Mn, int Cin, int KP, float extent, float ext2,
     int influence, float *__restrict__ wf, float *__restrict__ kp_min, int *__restrict__ kp_arg)
 {
-    __shared__ __attribute__((aligned(16))) float s_w[KD_BLOCK / 64][KD_NCH][KD_MAX];
-    __shared__ __attribute__((aligned(16))) float4 s_rel[KD_BLOCK / 64][KD_NCH];
-    __shared__ int s_id[KD_BLOCK / 64][KD_NCH];
+    __shared__ __attribute__((aligned(16))) float s_w[KP_BLOCK / 64][KP_NCH][KP_MAX];
+    __shared__ __attribute__((aligned(16))) float4 s_rel[KP_BLOCK / 64][KP_NCH];
+    __shared__ int s_id[KP_BLOCK / 64][KP_NCH];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t q = (int64_t)blockIdx.x * (KD_BLOCK / 64) + wave;
+    const int64_t q = (int64_t)blockIdx.x * (KP_BLOCK / 64) + wave;
     if (q >= Nq) return;  // wave-uniform
-    float(*w)[KD_MAX] = s_w[wave];
+    float(*w)[KP_MAX] = s_w[wave];
     float4 *rel = s_rel[wave];
     int *ids = s_id[wave];
     const float qx = query[q * 3 + 0], qy = query[q * 3 + 1], qz = query[q * 3 + 2];
-    const KdInfluence infl = kd_influence(extent, ext2, influence);
+    const KpInfluence infl = kp_influence(extent, influence, ext2);
     const int k = lane & 15, nsub = lane >> 4;
     const bool kreal = k < KP;
     float kx = 0.0f, ky = 0.0f, kz = 0.0f;
@@ -242,18 +153,19 @@ __global__ __launch_bounds__(KD_BLOCK) void kpconv_deform_fma_kernel(
     }
     float best = 3.0e38f;
     int barg = 0;
-    const bool single_pass = Mn <= KD_NCH;  // then the weights of phase A serve every channel chunk
+    const bool single_pass = Mn <= KP_NCH;  // then the weights of phase A serve every channel chunk
     for (int c0 = 0; c0 < Cin; c0 += 64) {
-        float acc[KD_MAX];
+        float acc[KP_MAX];
 #pragma unroll
-        for (int kk = 0; kk < KD_MAX; ++kk) acc[kk] = 0.0f;
+        for (int kk = 0; kk < KP_MAX; ++kk) acc[kk] = 0.0f;
         const int c = c0 + lane;
-        for (int n0 = 0; n0 < Mn; n0 += KD_NCH) {
-            const int cnt = min(KD_NCH, Mn - n0);
-            const int cntg = (cnt + KD_GROUP - 1) / KD_GROUP * KD_GROUP;  // rows [cnt, cntg): zero weights
+        for (int n0 = 0; n0 < Mn; n0 += KP_NCH) {
+            const int cnt = min(KP_NCH, Mn - n0);
+            const int cntg = (cnt + KP_GROUP - 1) / KP_GROUP * KP_GROUP;  // rows [cnt, cntg): zero weights
             if (!(single_pass && c0 > 0)) {
-                kd_fetch_neighbours(support, nbr + q * Mn + n0, cnt, cntg, M, qx, qy, qz, rel, ids, lane);
-                kd_lds_sync();
+                kp_fetch_neighbours(support, nbr + q * Mn + n0, cnt, cntg, M, qx, qy, qz, kd_shadow_rel(qx, qy, qz), rel, ids,
+                                    lane);
+                wave_lds_sync();
                 for (int n = nsub; n < cntg; n += 4) {  // the same trip count in every lane: cntg is a multiple of 16
                     const float4 r = rel[n];
                     const float dx = r.x - kx, dy = r.y - ky, dz = r.z - kz;
@@ -267,35 +179,14 @@ __global__ __launch_bounds__(KD_BLOCK) void kpconv_deform_fma_kernel(
                         barg = n0 + n;
                     }
                 }
-                kd_lds_sync();
+                wave_lds_sync();
             }
-            if (c < Cin) {
-                for (int g0 = 0; g0 < cntg; g0 += KD_GROUP) {
-                    float v[KD_GROUP];
-#pragma unroll
-                    for (int u = 0; u < KD_GROUP; ++u)  // shadow rows carry zero weights: row 0 stands in for them
-                        v[u] = feat[(size_t)max(ids[g0 + u], 0) * Cin + c];
-#pragma unroll
-                    for (int u = 0; u < KD_GROUP; ++u) {
-                        const float *wr = &w[g0 + u][0];
-                        const float4 w0 = *reinterpret_cast<const float4 *>(wr), w1 = *reinterpret_cast<const float4 *>(wr + 4);
-                        const float4 w2 = *reinterpret_cast<const float4 *>(wr + 8), w3 = *reinterpret_cast<const float4 *>(wr + 12);
-                        acc[0] = __builtin_fmaf(w0.x, v[u], acc[0]);   acc[1] = __builtin_fmaf(w0.y, v[u], acc[1]);
-                        acc[2] = __builtin_fmaf(w0.z, v[u], acc[2]);   acc[3] = __builtin_fmaf(w0.w, v[u], acc[3]);
-                        acc[4] = __builtin_fmaf(w1.x, v[u], acc[4]);   acc[5] = __builtin_fmaf(w1.y, v[u], acc[5]);
-                        acc[6] = __builtin_fmaf(w1.z, v[u], acc[6]);   acc[7] = __builtin_fmaf(w1.w, v[u], acc[7]);
-                        acc[8] = __builtin_fmaf(w2.x, v[u], acc[8]);   acc[9] = __builtin_fmaf(w2.y, v[u], acc[9]);
-                        acc[10] = __builtin_fmaf(w2.z, v[u], acc[10]); acc[11] = __builtin_fmaf(w2.w, v[u], acc[11]);
-                        acc[12] = __builtin_fmaf(w3.x, v[u], acc[12]); acc[13] = __builtin_fmaf(w3.y, v[u], acc[13]);
-                        acc[14] = __builtin_fmaf(w3.z, v[u], acc[14]); acc[15] = __builtin_fmaf(w3.w, v[u], acc[15]);
-                    }
-                }
-            }
-            kd_lds_sync();
+            if (c < Cin) kp_fma_rows(feat, ids, w, cntg, Cin, c, acc);
+            wave_lds_sync();
         }
         if (c < Cin) {
 #pragma unroll
-            for (int kk = 0; kk < KD_MAX; ++kk)
+            for (int kk = 0; kk < KP_MAX; ++kk)
                 if (kk < KP) wf[((size_t)q * KP + kk) * Cin + c] = acc[kk] * (mods ? mods[q * KP + kk] : 1.0f);
         }
     }
@@ -320,20 +211,20 @@ __global__ __launch_bounds__(KD_BLOCK) void kpconv_deform_fma_kernel(
 //      reduced over the 16 neighbour lanes by a fixed xor tree.
 // The arg-min term  d_kp_min[k] * (-2) (rel[arg] - dk)  is added by the storing lane.
 template <bool VEC4>
-__global__ __launch_bounds__(KD_BLOCK) void kpconv_deform_bwd_kernel(
+__global__ __launch_bounds__(KP_BLOCK) void kpconv_deform_bwd_kernel(
     const float *__restrict__ query, const float *__restrict__ support, const int64_t *__restrict__ nbr,
     const float *__restrict__ feat, const float *__restrict__ kpts, const float *__restrict__ offsets,
     const float *__restrict__ mods, const float *__restrict__ d_wf, const float *__restrict__ d_kp_min,
     const int *__restrict__ kp_arg, int64_t Nq, int64_t M, int Mn, int Cin, int KP, float extent, float ext2,
     int influence, float *__restrict__ gslots, float *__restrict__ d_off, float *__restrict__ d_mod)
 {
-    __shared__ float s_w[KD_BLOCK / 64][KD_NMAX][KD_WPAD];
-    __shared__ __attribute__((aligned(16))) float4 s_rel[KD_BLOCK / 64][KD_NMAX];
-    __shared__ __attribute__((aligned(16))) float4 s_dk[KD_BLOCK / 64][KD_MAX];  // deformed kernel point, modulation
-    __shared__ int s_id[KD_BLOCK / 64][KD_NMAX];
-    __shared__ float s_msk[KD_BLOCK / 64][KD_NMAX];
+    __shared__ float s_w[KP_BLOCK / 64][KP_NMAX][KD_WPAD];
+    __shared__ __attribute__((aligned(16))) float4 s_rel[KP_BLOCK / 64][KP_NMAX];
+    __shared__ __attribute__((aligned(16))) float4 s_dk[KP_BLOCK / 64][KP_MAX];  // deformed kernel point, modulation
+    __shared__ int s_id[KP_BLOCK / 64][KP_NMAX];
+    __shared__ float s_msk[KP_BLOCK / 64][KP_NMAX];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t q = (int64_t)blockIdx.x * (KD_BLOCK / 64) + wave;
+    const int64_t q = (int64_t)blockIdx.x * (KP_BLOCK / 64) + wave;
     if (q >= Nq) return;  // wave-uniform
     float(*w)[KD_WPAD] = s_w[wave];
     float4 *rel = s_rel[wave];
@@ -341,7 +232,7 @@ __global__ __launch_bounds__(KD_BLOCK) void kpconv_deform_bwd_kernel(
     int *ids = s_id[wave];
     float *msk = s_msk[wave];
     const float qx = query[q * 3 + 0], qy = query[q * 3 + 1], qz = query[q * 3 + 2];
-    const KdInfluence infl = kd_influence(extent, ext2, influence);
+    const KpInfluence infl = kp_influence(extent, influence, ext2);
     const int k16 = lane & 15, g = lane >> 4;
     const bool kreal = k16 < KP;
     float kx = 0.0f, ky = 0.0f, kz = 0.0f, kmod = 0.0f;
@@ -352,17 +243,17 @@ __global__ __launch_bounds__(KD_BLOCK) void kpconv_deform_bwd_kernel(
         kz = o[2] + kpts[k16 * 3 + 2];
         kmod = mods ? mods[q * KP + k16] : 1.0f;
     }
-    if (lane < KD_MAX) dkp[lane] = make_float4(kx, ky, kz, kmod);
+    if (lane < KP_MAX) dkp[lane] = make_float4(kx, ky, kz, kmod);
     const float *__restrict__ dq = d_wf + (size_t)q * KP * Cin;  // this query's (KP, Cin) gradient block
     float gx[4], gy[4], gz[4], gm[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) gx[j] = gy[j] = gz[j] = gm[j] = 0.0f;
 
-    for (int n0 = 0; n0 < Mn; n0 += KD_NMAX) {
-        const int cnt = min(KD_NMAX, Mn - n0);
+    for (int n0 = 0; n0 < Mn; n0 += KP_NMAX) {
+        const int cnt = min(KP_NMAX, Mn - n0);
         const int nblk = (cnt + 15) / 16;  // 16-neighbour blocks (wave-uniform)
-        kd_fetch_neighbours(support, nbr + q * Mn + n0, cnt, 64, M, qx, qy, qz, rel, ids, lane);
-        kd_lds_sync();
+        kp_fetch_neighbours(support, nbr + q * Mn + n0, cnt, 64, M, qx, qy, qz, kd_shadow_rel(qx, qy, qz), rel, ids, lane);
+        wave_lds_sync();
         // (b) weights and masks, lane = (kernel point k16, neighbour 4 s + g)
         for (int s = 0; s < 4 * nblk; ++s) {
             const int n = 4 * s + g;
@@ -375,7 +266,7 @@ __global__ __launch_bounds__(KD_BLOCK) void kpconv_deform_bwd_kernel(
             w[n][k16] = (valid && live) ? kd_h(d2, infl) * kmod : 0.0f;
             if (k16 == 0) msk[n] = live ? 1.0f : 0.0f;
         }
-        kd_lds_sync();
+        wave_lds_sync();
         // (c) per-slot gradient rows
         if (gslots) {
             float aw[4][4];  // A operand: w[n = 16 nb + k16][k = 4 s + g]
@@ -391,7 +282,7 @@ __global__ __launch_bounds__(KD_BLOCK) void kpconv_deform_bwd_kernel(
 #pragma unroll
                 for (int nb = 0; nb < 4; ++nb)
                     if (nb < nblk) {
-                        kd_f32x4 acc = (kd_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+                        f32x4 acc = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
                         for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[nb][s], bd[s], acc, 0, 0, 0);
 #pragma unroll
@@ -403,9 +294,9 @@ __global__ __launch_bounds__(KD_BLOCK) void kpconv_deform_bwd_kernel(
             }
         }
         // (d) sensitivities S[k][n] over the channels, then the offset / modulation gradients
-        kd_f32x4 sacc[4];
+        f32x4 sacc[4];
 #pragma unroll
-        for (int nb = 0; nb < 4; ++nb) sacc[nb] = (kd_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+        for (int nb = 0; nb < 4; ++nb) sacc[nb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
         int idn[4];
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) idn[nb] = nb < nblk ? ids[16 * nb + k16] : -1;
@@ -466,7 +357,7 @@ __global__ __launch_bounds__(KD_BLOCK) void kpconv_deform_bwd_kernel(
                     gz[j] += sv * dz;
                 }
             }
-        kd_lds_sync();  // the next chunk overwrites the tiles
+        wave_lds_sync();  // the next chunk overwrites the tiles
     }
 #pragma unroll
     for (int off = 1; off < 16; off <<= 1) {
@@ -521,30 +412,23 @@ TP3D_EXPORT int tp3d_kpconv_deform_weighted_f32(const float *query, const float 
                                                 float extent, int influence, float *weighted, float *kp_min_d2,
                                                 int32_t *kp_argmin, void *stream)
 {
-    if (Nq < 0 || M <= 0 || Mn <= 0 || Cin <= 0 || KP <= 0 || influence < 0 || influence > 2) return TP3D_E_BADARG;
-    if (KP > KD_MAX) return TP3D_E_TOOBIG;
+    if (int rc = kp_check_args(Nq, M, Mn, Cin, KP, influence, 1)) return rc;
     if (Nq == 0) return TP3D_OK;
     if (!query || !support || !neighbors || !features || !k_points || !offsets || !weighted) return TP3D_E_BADARG;
     if (kp_argmin && !kp_min_d2) return TP3D_E_BADARG;
-    const int64_t blocks = (Nq + KD_BLOCK / 64 - 1) / (KD_BLOCK / 64);
-    if (blocks > 0x7fffffff) return TP3D_E_TOOBIG;
     hipStream_t s = (hipStream_t)stream;
     const float ext2 = kd_ext2(extent);
-    if (Mn <= KD_NMAX && M * (int64_t)Cin < ((int64_t)1 << 30)) {
-        const int passes = (Cin + 16 * KD_CB - 1) / (16 * KD_CB);
-        const bool spread = passes > 1 && Nq <= 4096;  // as the rigid kernel: one wave per (query, 64 channels)
-        const dim3 grid((unsigned)blocks, spread ? passes : 1);
-        const int cpass = spread ? 16 * KD_CB : Cin;
-        if (Mn <= 32)
-            hipLaunchKernelGGL(kpconv_deform_mfma_kernel<8>, grid, dim3(KD_BLOCK), 0, s, query, support, neighbors, features,
-                               k_points, offsets, modulations, Nq, M, Mn, Cin, KP, extent, ext2, influence, cpass, weighted,
-                               kp_min_d2, kp_argmin);
-        else
-            hipLaunchKernelGGL(kpconv_deform_mfma_kernel<16>, grid, dim3(KD_BLOCK), 0, s, query, support, neighbors, features,
-                               k_points, offsets, modulations, Nq, M, Mn, Cin, KP, extent, ext2, influence, cpass, weighted,
-                               kp_min_d2, kp_argmin);
-    } else
-        hipLaunchKernelGGL(kpconv_deform_fma_kernel, dim3((unsigned)blocks), dim3(KD_BLOCK), 0, s, query, support, neighbors,
+    const KpMfmaRoute r = kp_mfma_route(Nq, M, Mn, Cin);
+    if (r.ok && !r.wide)
+        hipLaunchKernelGGL(kpconv_deform_mfma_kernel<8>, r.grid, dim3(KP_BLOCK), 0, s, query, support, neighbors, features,
+                           k_points, offsets, modulations, Nq, M, Mn, Cin, KP, extent, ext2, influence, r.cpass, weighted,
+                           kp_min_d2, kp_argmin);
+    else if (r.ok)
+        hipLaunchKernelGGL(kpconv_deform_mfma_kernel<16>, r.grid, dim3(KP_BLOCK), 0, s, query, support, neighbors, features,
+                           k_points, offsets, modulations, Nq, M, Mn, Cin, KP, extent, ext2, influence, r.cpass, weighted,
+                           kp_min_d2, kp_argmin);
+    else
+        hipLaunchKernelGGL(kpconv_deform_fma_kernel, kp_query_grid(Nq), dim3(KP_BLOCK), 0, s, query, support, neighbors,
                            features, k_points, offsets, modulations, Nq, M, Mn, Cin, KP, extent, ext2, influence, weighted,
                            kp_min_d2, kp_argmin);
     return check_launch();
@@ -558,8 +442,7 @@ TP3D_EXPORT int tp3d_kpconv_deform_bwd_f32(const float *query, const float *supp
                                            float *d_modulations, void *inverse, size_t inverse_bytes, int inverse_ready,
                                            void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (Nq < 0 || M <= 0 || Mn <= 0 || Cin <= 0 || KP <= 0 || influence < 0 || influence > 2) return TP3D_E_BADARG;
-    if (KP > KD_MAX) return TP3D_E_TOOBIG;
+    if (int rc = kp_check_args(Nq, M, Mn, Cin, KP, influence, 1)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (Nq == 0) return d_features ? zero_async(d_features, (size_t)M * Cin * sizeof(float), s) : TP3D_OK;
     if (!query || !support || !neighbors || !features || !k_points || !offsets || !d_weighted || !d_offsets)
@@ -568,7 +451,6 @@ TP3D_EXPORT int tp3d_kpconv_deform_bwd_f32(const float *query, const float *supp
     if (d_modulations && !modulations) return TP3D_E_BADARG;
     const int64_t slots = Nq * Mn;
     if (slots > INT32_MAX || M > INT32_MAX / 2) return TP3D_E_TOOBIG;
-    const int64_t blocks = (Nq + KD_BLOCK / 64 - 1) / (KD_BLOCK / 64);
     int *start = nullptr, *order = nullptr;
     float *g = nullptr;
     if (d_features) {
@@ -581,11 +463,11 @@ TP3D_EXPORT int tp3d_kpconv_deform_bwd_f32(const float *query, const float *supp
     const float ext2 = kd_ext2(extent);
     const bool vec4 = Cin % 4 == 0 && ((uintptr_t)features % 16 == 0) && ((uintptr_t)d_weighted % 16 == 0);
     if (vec4)
-        hipLaunchKernelGGL(kpconv_deform_bwd_kernel<true>, dim3((unsigned)blocks), dim3(KD_BLOCK), 0, s, query, support,
+        hipLaunchKernelGGL(kpconv_deform_bwd_kernel<true>, kp_query_grid(Nq), dim3(KP_BLOCK), 0, s, query, support,
                            neighbors, features, k_points, offsets, modulations, d_weighted, d_kp_min_d2, kp_argmin, Nq, M, Mn,
                            Cin, KP, extent, ext2, influence, g, d_offsets, d_modulations);
     else
-        hipLaunchKernelGGL(kpconv_deform_bwd_kernel<false>, dim3((unsigned)blocks), dim3(KD_BLOCK), 0, s, query, support,
+        hipLaunchKernelGGL(kpconv_deform_bwd_kernel<false>, kp_query_grid(Nq), dim3(KP_BLOCK), 0, s, query, support,
                            neighbors, features, k_points, offsets, modulations, d_weighted, d_kp_min_d2, kp_argmin, Nq, M, Mn,
                            Cin, KP, extent, ext2, influence, g, d_offsets, d_modulations);
     if (int rc = check_launch()) return rc;

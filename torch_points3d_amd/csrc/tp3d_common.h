@@ -73,12 +73,12 @@ int csr_transpose(const int64_t *idx, int B, int L, int nbins, int div, const fl
 int gather_sum(const float *rows, const int *start, const int *order, const float *wsorted, int B, int C, int nbins,
                int Lrow, int Lslots, float *out, hipStream_t s);
 
-// kpconv.hip: multi-workgroup inverse of an index table (cnt, cursor: M ints; start: M + 1; order: slots).
+// nbr_table.hip: multi-workgroup inverse of an index table (cnt, cursor: M ints; start: M + 1; order: slots).
 // per_cloud_slots > 0: idx is (clouds, per_cloud_slots) with values clamped to [0, per_cloud_bins); bin = cloud *
 // per_cloud_bins + value, M = clouds * per_cloud_bins (one flat table over the batch).
 int invert_table(const int64_t *idx, int64_t slots, int64_t M, int *cnt, int *start, int *cursor, int *order,
                  hipStream_t s, int64_t per_cloud_slots = 0, int64_t per_cloud_bins = 0, int *merge_tmp = nullptr);
-// kpconv.hip: the inverted neighbour table inside a tp3d_kpconv_bwd_workspace_bytes(M, slots) buffer (built unless
+// nbr_table.hip: the inverted neighbour table inside a tp3d_kpconv_bwd_workspace_bytes(M, slots) buffer (built unless
 // `ready`), and the per-support-point sum of per-slot gradient rows through it (ascending slot order)
 int invert_neighbors(const int64_t *neighbors, int64_t slots, int64_t M, void *workspace, int **start_out,
                      int **order_out, hipStream_t s, bool ready = false);

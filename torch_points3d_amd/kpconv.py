@@ -3,7 +3,8 @@
 Mirrors `KPConv_ops` (torch_points3d/modules/KPConv/convolution_ops.py:19-107) and `KPConvLayer`
 (modules/KPConv/kernels.py:20-104): same arguments, same shadow-neighbour convention (-1 -> zero feature), same
 influence / aggregation modes, same parameter names (`K_points`, `weight`).  Stage 1 (kernel-point weighted
-neighbourhood features) and its backward are HIP kernels (csrc/kpconv.hip); stage 2 is the single
+neighbourhood features) and its backward are HIP kernels (csrc/kpconv.hip; the inverted neighbour table the backward
+sums through is csrc/nbr_table.hip); stage 2 is the single
 (Nq, KP*Cin) x (KP*Cin, Cout) GEMM the reference's permute/matmul/sum amounts to; the kernel-weight gradient runs
 on the split-K MFMA kernel (csrc/gemm_tn.hip).  Differentiable wrt `features` and `K_values` (what the reference
 trains); positions and kernel points carry no gradient (kernels.py:57-59 sets requires_grad=False on K_points).
@@ -11,7 +12,11 @@ trains); positions and kernel points carry no gradient (kernels.py:57-59 sets re
 The deformable convolution (`KPConv_deform_ops`, convolution_ops.py:110-235; `KPConvDeformableLayer`,
 kernels.py:107-256) runs on csrc/kpconv_deform.hip: per-query kernel points, in-range mask, modulations and the
 fitting-loss distances in the forward kernel; gradients wrt features, offsets and modulations in one backward kernel.
+The per-query device code, the argument checks and the kernel routing the two share are in csrc/kp_common.h; here they
+share the device check, the buffers of the features gradient and the layers' base class.
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -19,6 +24,30 @@ from . import _lib
 from .fused import gemm_tn
 
 _INFLUENCE = {"constant": 0, "linear": 1, "gaussian": 2}
+
+
+def _require_gpu(*tensors):
+    for t in tensors:
+        if t is not None and t.device.type != "cuda":
+            raise RuntimeError("torch_points3d_amd runs on MI355X only: got a %s tensor (no CPU fallback is provided)"
+                               % t.device.type)
+
+
+@contextlib.contextmanager
+def _features_grad(nbr, M, Cin, dev, wanted=True):
+    """What the gradient wrt the features needs around the backward call: yields `(dx, tail)`, the (M, Cin) result and the
+    trailing `inverse, inverse_bytes, inverse_ready, workspace, workspace_bytes` arguments of the entry point (the
+    inverse of the neighbour table and the `kpconv_bwd` scratch of per-slot gradient rows); on leaving the block the
+    inverse the call has built is published.  `wanted=False`: no features gradient, all of it null."""
+    if not wanted:
+        yield None, (None, 0, 0, None, 0)
+        return
+    dx = torch.empty((M, Cin), dtype=torch.float32, device=dev)
+    nbytes = _lib.load().tp3d_kpconv_grad_workspace_bytes(M, nbr.numel(), Cin)
+    ws = _lib.workspace("kpconv_bwd", nbytes, dev)
+    inv, inv_bytes, ready, token = _lib.neighbour_inverse(nbr, M, dev)
+    yield dx, (_lib.ptr(inv), inv_bytes, ready, _lib.ptr(ws), nbytes)
+    _lib.inverse_built(token, dev)
 
 
 class _KPConv(torch.autograd.Function):
@@ -51,15 +80,10 @@ class _KPConv(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             d_wf = torch.mm(d_out, W.reshape(KP * Cin, -1).t())  # (Nq, KP*Cin)
-            dx = torch.empty((M, Cin), dtype=torch.float32, device=dev)
-            nbytes = _lib.load().tp3d_kpconv_grad_workspace_bytes(M, Nq * Mn, Cin)
-            ws = _lib.workspace("kpconv_bwd", nbytes, dev)
-            with _lib.on_device(dev):
-                inv, inv_bytes, ready, token = _lib.neighbour_inverse(nbr, M, dev)
+            with _lib.on_device(dev), _features_grad(nbr, M, Cin, dev) as (dx, tail):
                 _lib.call("tp3d_kpconv_bwd_features_f32", _lib.ptr(query), _lib.ptr(support), _lib.ptr(nbr), _lib.ptr(kp),
-                          _lib.ptr(d_wf), Nq, M, Mn, Cin, KP, extent, influence, closest, _lib.ptr(dx), _lib.ptr(inv),
-                          inv_bytes, ready, _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
-                _lib.inverse_built(token, dev)
+                          _lib.ptr(d_wf), Nq, M, Mn, Cin, KP, extent, influence, closest, _lib.ptr(dx), *tail,
+                          _lib.stream_ptr(dev))
         return dx, dW, None, None, None, None, None, None, None
 
 
@@ -69,10 +93,7 @@ def KPConv_ops(query_points, support_points, neighbors_indices, features, K_poin
         raise ValueError("Unknown influence function type (config.KP_influence)")
     if aggregation_mode not in ("sum", "closest"):
         raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
-    for t in (query_points, support_points, neighbors_indices, features, K_points, K_values):
-        if t.device.type != "cuda":
-            raise RuntimeError("torch_points3d_amd runs on MI355X only: got a %s tensor (no CPU fallback is provided)"
-                               % t.device.type)
+    _require_gpu(query_points, support_points, neighbors_indices, features, K_points, K_values)
     q = query_points.detach().float().contiguous()
     s = support_points.detach().float().contiguous()
     nbr = neighbors_indices.long().contiguous()
@@ -119,20 +140,11 @@ class _KPConvDeform(torch.autograd.Function):
             d_kp_min = None if d_kp_min is None else d_kp_min.float().contiguous()
             d_off = torch.empty((Nq, KP, 3), dtype=torch.float32, device=dev)
             d_mod = torch.empty((Nq, KP), dtype=torch.float32, device=dev) if mod is not None else None
-            inv = ws = None
-            inv_bytes = nbytes = ready = 0
-            token = None
-            with _lib.on_device(dev):
-                if need[0]:
-                    dx = torch.empty((M, Cin), dtype=torch.float32, device=dev)
-                    nbytes = _lib.load().tp3d_kpconv_grad_workspace_bytes(M, Nq * Mn, Cin)
-                    ws = _lib.workspace("kpconv_bwd", nbytes, dev)
-                    inv, inv_bytes, ready, token = _lib.neighbour_inverse(nbr, M, dev)
+            with _lib.on_device(dev), _features_grad(nbr, M, Cin, dev, need[0]) as (dx, tail):
                 _lib.call("tp3d_kpconv_deform_bwd_f32", _lib.ptr(query), _lib.ptr(support), _lib.ptr(nbr), _lib.ptr(x),
                           _lib.ptr(kp), _lib.ptr(off), _lib.ptr(mod), _lib.ptr(d_wf), _lib.ptr(d_kp_min), _lib.ptr(kp_arg),
-                          Nq, M, Mn, Cin, KP, extent, influence, _lib.ptr(dx), _lib.ptr(d_off), _lib.ptr(d_mod),
-                          _lib.ptr(inv), inv_bytes, ready, _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
-                _lib.inverse_built(token, dev)
+                          Nq, M, Mn, Cin, KP, extent, influence, _lib.ptr(dx), _lib.ptr(d_off), _lib.ptr(d_mod), *tail,
+                          _lib.stream_ptr(dev))
             if not need[2]:
                 d_off = None
             if not need[3]:
@@ -164,13 +176,7 @@ def KPConv_deform_ops(query_points, support_points, neighbors_indices, features,
                                   "convolution (the reference raises on it as well); use 'sum'")
     if aggregation_mode != "sum":
         raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
-    tensors = [query_points, support_points, neighbors_indices, features, K_points, offsets, K_values]
-    if modulations is not None:
-        tensors.append(modulations)
-    for t in tensors:
-        if t.device.type != "cuda":
-            raise RuntimeError("torch_points3d_amd runs on MI355X only: got a %s tensor (no CPU fallback is provided)"
-                               % t.device.type)
+    _require_gpu(query_points, support_points, neighbors_indices, features, K_points, offsets, K_values, modulations)
     if support_points.shape[0] == 0 or neighbors_indices.shape[1] == 0:
         raise ValueError("KPConv_deform_ops needs at least one support point and one neighbour slot")
     q = query_points.detach().float().contiguous()
@@ -205,17 +211,13 @@ def default_kernel_points(num_points=15, iterations=400):
     return torch.from_numpy(np.concatenate([np.zeros((1, 3)), p], axis=0).astype(np.float32))
 
 
-class KPConvLayer(nn.Module):
-    """Kernel-point convolution layer with the reference's parameters (`K_points` frozen, `weight` (KP, Cin, Cout)
-    xavier-normal) and forward signature (modules/KPConv/kernels.py:20-104).  The kernel-point disposition file of the
-    reference is not shipped here: pass `K_points` (KP, 3), e.g. taken from a reference checkpoint or generated by
-    the reference's `load_kernels`."""
+class _KPConvBase(nn.Module):
+    """What the rigid and the deformable layer share: the reference's constructor fields, the frozen `K_points`, the
+    xavier-normal (KP, Cin, .) parameters and the `add_one` column of ones."""
 
     _INFLUENCE_TO_RADIUS = 1.5
 
-    def __init__(self, num_inputs, num_outputs, point_influence, K_points, KP_influence="linear",
-                 aggregation_mode="sum", add_one=False, **kwargs):
-        # **kwargs: n_kernel_points / fixed / dimension of the reference's YAML are implied by K_points here
+    def __init__(self, num_inputs, num_outputs, point_influence, K_points, KP_influence, aggregation_mode, add_one):
         super().__init__()
         self.kernel_radius = self._INFLUENCE_TO_RADIUS * point_influence
         self.point_influence = point_influence
@@ -227,19 +229,38 @@ class KPConvLayer(nn.Module):
         K_points = torch.as_tensor(K_points, dtype=torch.float32)
         self.n_kernel_points = K_points.shape[0]
         self.K_points = nn.Parameter(K_points.clone(), requires_grad=False)
-        w = torch.empty([self.n_kernel_points, self.num_inputs, num_outputs], dtype=torch.float32)
-        nn.init.xavier_normal_(w)
-        self.weight = nn.Parameter(w)
 
-    def forward(self, query_points, support_points, neighbors, x):
+    def _xavier(self, width):
+        w = torch.empty([self.n_kernel_points, self.num_inputs, width], dtype=torch.float32)
+        nn.init.xavier_normal_(w)
+        return nn.Parameter(w)
+
+    def _features(self, support_points, x):
         if self.add_one:
             ones = torch.ones(support_points.shape[0], 1, dtype=torch.float32, device=support_points.device)
             x = ones if x is None else torch.cat([ones, x.float()], dim=-1)
+        return x
+
+
+class KPConvLayer(_KPConvBase):
+    """Kernel-point convolution layer with the reference's parameters (`K_points` frozen, `weight` (KP, Cin, Cout)
+    xavier-normal) and forward signature (modules/KPConv/kernels.py:20-104).  The kernel-point disposition file of the
+    reference is not shipped here: pass `K_points` (KP, 3), e.g. taken from a reference checkpoint or generated by
+    the reference's `load_kernels`."""
+
+    def __init__(self, num_inputs, num_outputs, point_influence, K_points, KP_influence="linear",
+                 aggregation_mode="sum", add_one=False, **kwargs):
+        # **kwargs: n_kernel_points / fixed / dimension of the reference's YAML are implied by K_points here
+        super().__init__(num_inputs, num_outputs, point_influence, K_points, KP_influence, aggregation_mode, add_one)
+        self.weight = self._xavier(num_outputs)
+
+    def forward(self, query_points, support_points, neighbors, x):
+        x = self._features(support_points, x)
         return KPConv_ops(query_points, support_points, neighbors, x, self.K_points, self.weight, self.point_influence,
                           self.KP_influence, self.aggregation_mode)
 
 
-class KPConvDeformableLayer(nn.Module):
+class KPConvDeformableLayer(_KPConvBase):
     """Deformable kernel-point convolution layer with the reference's parameters and forward
     (modules/KPConv/kernels.py:107-256): `K_points` frozen, `offset_weights` (KP, Cin, 3 KP or 4 KP when `modulated`)
     xavier-normal, `offset_bias` zeros, `weight` (KP, Cin, Cout).  A rigid convolution with `offset_weights` predicts
@@ -252,39 +273,21 @@ class KPConvDeformableLayer(nn.Module):
     FITTING_LOSS_KEY = "fitting_loss"
     REPULSION_LOSS_KEY = "repulsion_loss"
 
-    _INFLUENCE_TO_RADIUS = 1.5
-
     def __init__(self, num_inputs, num_outputs, point_influence, K_points, KP_influence="linear", aggregation_mode="sum",
                  modulated=False, loss_mode="fitting", add_one=False, **kwargs):
         # **kwargs: n_kernel_points / fixed / dimension of the reference's YAML are implied by K_points here
-        super().__init__()
-        self.kernel_radius = self._INFLUENCE_TO_RADIUS * point_influence
-        self.point_influence = point_influence
-        self.add_one = add_one
-        self.num_inputs = num_inputs + int(add_one)
-        self.num_outputs = num_outputs
-        self.KP_influence = KP_influence
-        self.aggregation_mode = aggregation_mode
+        super().__init__(num_inputs, num_outputs, point_influence, K_points, KP_influence, aggregation_mode, add_one)
         self.modulated = modulated
         self.internal_losses = {self.PERMISSIVE_LOSS_KEY: 0.0, self.FITTING_LOSS_KEY: 0.0, self.REPULSION_LOSS_KEY: 0.0}
         self.loss_mode = loss_mode
-        K_points = torch.as_tensor(K_points, dtype=torch.float32)
-        self.n_kernel_points = K_points.shape[0]
-        self.K_points = nn.Parameter(K_points.clone(), requires_grad=False)
         offset_dim = (4 if modulated else 3) * self.n_kernel_points
-        offset_weights = torch.empty([self.n_kernel_points, self.num_inputs, offset_dim], dtype=torch.float32)
-        nn.init.xavier_normal_(offset_weights)
-        self.offset_weights = nn.Parameter(offset_weights)
+        self.offset_weights = self._xavier(offset_dim)
         self.offset_bias = nn.Parameter(torch.zeros(offset_dim, dtype=torch.float32))
-        w = torch.empty([self.n_kernel_points, self.num_inputs, num_outputs], dtype=torch.float32)
-        nn.init.xavier_normal_(w)
-        self.weight = nn.Parameter(w)
+        self.weight = self._xavier(num_outputs)
 
     def forward(self, query_points, support_points, neighbors, x):
         from . import kpconv_losses as _losses
-        if self.add_one:
-            ones = torch.ones(support_points.shape[0], 1, dtype=torch.float32, device=support_points.device)
-            x = ones if x is None else torch.cat([ones, x.float()], dim=-1)
+        x = self._features(support_points, x)
         offset_feat = KPConv_ops(query_points, support_points, neighbors, x, self.K_points, self.offset_weights,
                                  self.point_influence, self.KP_influence, self.aggregation_mode) + self.offset_bias
         KP = self.n_kernel_points
