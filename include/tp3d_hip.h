@@ -35,7 +35,7 @@ extern "C" {
 #define TP3D_E_UNSORTED (-3) /* reserved: batch vector not sorted (checked by the host wrapper) */
 #define TP3D_E_TOOBIG (-4)   /* size exceeds what the kernel's index arithmetic supports */
 
-#define TP3D_ABI_VERSION 37
+#define TP3D_ABI_VERSION 38
 
 int tp3d_abi_version(void);
 const char *tp3d_strerror(int code);
@@ -48,6 +48,21 @@ int tp3d_last_hip_error(void);
  */
 #define TP3D_FPS_MAX_REG_POINTS 32768
 int tp3d_fps_f32(const float *xyz, int B, int N, int npoint, float *scratch, int64_t *out_idx, void *stream);
+
+/*
+ * fps(pos, batch, ratio) on a ragged batch      [reference call: core/spatial_ops/sampling.py:53-63 (FPSSampler)]
+ *   pos (M,3) f32; cloud b owns the rows seg_in[b] .. seg_in[b+1]) and selects seg_out[b+1] - seg_out[b] of them
+ *   (seg_in, seg_out: (clouds+1) int64 DEVICE arrays of offsets).  out_idx (seg_out[clouds]) int64 receives GLOBAL
+ *   row indices in selection order at out_idx[seg_out[b] ..].  One workgroup per cloud, the arithmetic of
+ *   tp3d_fps_f32: first selected = the cloud's first row, running min of (dx*dx+dy*dy)+dz*dz, ties -> lowest index;
+ *   equal clouds give tp3d_fps_f32's indices (+ the cloud's first row) bit for bit.
+ *   max_cloud_points: the largest cloud (picks the register template; a larger cloud than stated writes nothing).
+ *   A cloud without points or with a quota of 0 writes nothing; a quota above the cloud's size is the caller's
+ *   error (the host wrapper raises; the kernel stops at the cloud's size).
+ *   scratch: M floats, used only when max_cloud_points > TP3D_FPS_MAX_REG_POINTS.
+ */
+int tp3d_fps_ragged_f32(const float *pos, const int64_t *seg_in, const int64_t *seg_out, int64_t M, int clouds,
+                        int max_cloud_points, float *scratch, int64_t *out_idx, void *stream);
 
 /*
  * ball_query(radius, nsample, x, y, mode="dense", sort)
@@ -475,6 +490,42 @@ int tp3d_nbr_maxpool_fwd_f32(const float *x, const int64_t *neighbors, int64_t N
 int tp3d_nbr_maxpool_bwd_f32(const float *grad_out, const int32_t *argmax, const int64_t *neighbors, int64_t Nq,
                              int64_t M, int Mn, int C, float *d_x, void *inverse, size_t inverse_bytes,
                              int inverse_ready, void *stream);
+
+/* =====================================================================================================
+ * Message-passing PointNet++ (modules/pointnet2/message_passing.py:9-31 SAModule = FPSSampler +
+ * MultiscaleRadiusNeighbourFinder + torch_geometric PointConv; core/base_conv/message_passing.py:132-151
+ * GlobalBaseModule): neighbourhoods of varying size as an edge list in CSR form.
+ * ===================================================================================================== */
+
+/* radius(x, y, r, batch_x, batch_y, max_num_neighbors) as edges      [core/spatial_ops/neighbour_finder.py:31-33,141-144]
+ *   table (Nq, max_num) int64: the -1 padded output of tp3d_ball_query_partial_dense_f32 (sort = 0).
+ *   edge_start (Nq+1) = exclusive scan of the number of slots >= 0 per row (edge_start[Nq] = E, which the caller
+ *   reads back to size col);  col (E) = the slots >= 0, row-major, in slot order (ascending support row). */
+int tp3d_table_edge_start_i64(const int64_t *table, int64_t Nq, int max_num, int64_t *edge_start, void *stream);
+int tp3d_table_edge_col_i64(const int64_t *table, const int64_t *edge_start, int64_t Nq, int max_num, int64_t E,
+                            int64_t *col, void *stream);
+
+/* message of PointConv: cat([x_j, pos_j - pos_i])                     [modules/pointnet2/message_passing.py:20,26]
+ *   for edge e of query i (edge_start[i] <= e < edge_start[i+1]) with support row j = col[e]:
+ *   out[e, :] = [ x[j, 0:C] | pos_s[j] - pos_q[i] | 0 .. ];  x (M,C) or NULL when C == 0, pos_s (M,3), pos_q (Nq,3),
+ *   out (E, ld), ld >= C+3; columns past C+3 are written as zeros (16-byte row alignment, as
+ *   tp3d_group_concat_fwd_f32).  A col outside [0, M) gives a zero row.  Gradient wrt x: tp3d_rows_scatter_bwd_f32
+ *   with B = 1, L = E, div = 1, idx = col, col0 = 0. */
+int tp3d_pointconv_rows_f32(const float *x, const float *pos_s, const float *pos_q, const int64_t *edge_start,
+                            const int64_t *col, int64_t Nq, int64_t M, int64_t E, int C, int ld, float *out,
+                            void *stream);
+
+/* max over segments of rows: aggr="max" of PointConv (seg = edge_start) and global_max_pool of GlobalBaseModule
+ * (seg = the cloud offsets)                                           [core/base_conv/message_passing.py:136,145]
+ *   rows (E, ld), seg (S+1) int64 ascending with seg[0] = 0, seg[S] = E -> out[s, c] = max over rows seg[s] ..
+ *   seg[s+1]) of rows[r, c], c < C <= ld; argmax (S,C) int64 = the winning row r (the first maximum); an empty
+ *   segment gives 0.0 and -1.
+ *   bwd: d_rows (E, ld) OVERWRITTEN: dout[s, c] at the winning row, zero elsewhere, padding columns zero.
+ *   Atomic-free (every row belongs to one segment), bitwise reproducible. */
+int tp3d_segment_max_fwd_f32(const float *rows, const int64_t *seg, int64_t S, int64_t E, int C, int ld, float *out,
+                             int64_t *argmax, void *stream);
+int tp3d_segment_max_bwd_f32(const float *dout, const int64_t *argmax, const int64_t *seg, int64_t S, int64_t E, int C,
+                             int ld, float *d_rows, void *stream);
 
 /* =====================================================================================================
  * Launch plans (host arithmetic only, no device work): what an entry point WILL do for given sizes -- how it

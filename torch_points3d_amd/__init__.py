@@ -2,14 +2,27 @@
 
 `torch_points3d_amd.torchpoints` serves the `torch_points_kernels` function API from hand-written HIP
 kernels (libtp3d_hip.so, C-ABI in include/tp3d_hip.h); `torch_points3d_amd.dense` / `.pointnet2` are the
-host-side mirror of the reference's dense PointNet++ modules that call it.
+host-side mirror of the reference's dense PointNet++ modules that call it; `.pointnet2_mp` is the message-passing
+PointNet++ (ragged batches: FPSSampler, SAModule, GlobalBaseModule, FPModule, PointNet2MP).
 """
 from .torchpoints import (  # noqa: F401
     ball_query,
+    fps_quota,
+    fps_ragged,
     furthest_point_sample,
     grouping_operation,
     three_interpolate,
     three_nn,
+)
+from .pointnet2_mp import (  # noqa: F401
+    FPModule,
+    FPSSampler,
+    GlobalBaseModule,
+    MultiscaleRadiusNeighbourFinder,
+    PointConv,
+    PointNet2MP,
+    RadiusNeighbourFinder,
+    SAModule,
 )
 
 __version__ = "0.1.0"

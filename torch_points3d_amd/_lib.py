@@ -70,6 +70,12 @@ SIGNATURES = {
     "tp3d_attn_pool_fwd_f32": [_p, _p, _p, _l, _i, _i, _i, _i, _p, _p],
     "tp3d_attn_pool_bwd_f32": [_p, _p, _p, _p, _l, _i, _i, _i, _i, _p, _p, _p],
     "tp3d_relation_rows_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p],
+    "tp3d_fps_ragged_f32": [_p, _p, _p, _l, _i, _i, _p, _p, _p],
+    "tp3d_table_edge_start_i64": [_p, _l, _i, _p, _p],
+    "tp3d_table_edge_col_i64": [_p, _p, _l, _i, _l, _p, _p],
+    "tp3d_pointconv_rows_f32": [_p, _p, _p, _p, _p, _l, _l, _l, _i, _i, _p, _p],
+    "tp3d_segment_max_fwd_f32": [_p, _p, _l, _l, _i, _i, _p, _p, _p],
+    "tp3d_segment_max_bwd_f32": [_p, _p, _p, _l, _l, _i, _i, _p, _p],
     # launch plans (host arithmetic; the last argument is a HOST int64 array)
     "tp3d_gemm_tn_plan": [_l, _i, _i, _p],
     "tp3d_gemm_tn_x3_plan": [_l, _i, _i, _p],
@@ -104,7 +110,7 @@ MISC = {
     "tp3d_voxel_workspace_bytes": (_z, [_l]),
     "tp3d_ball_query_workspace_bytes": (_z, [_i, _l, _i]),
 }
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 _handle = None
 

@@ -85,9 +85,16 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 // BLOCK threads, P (even) points per thread: point j = t + k*BLOCK lives in thread t, slot k; slots are held
 // as P/2 register PAIRS so the distance arithmetic issues as packed fp32 (v_pk_add/mul_f32, 2 points per
 // instruction -- the kernel is VALU-issue bound, not memory bound).
-template <int BLOCK, int P>
+//
+// RAGGED (tp3d_fps_ragged_f32): cloud b owns the rows seg_in[b] .. seg_in[b+1]) of xyz (M, 3) and selects
+// seg_out[b+1] - seg_out[b] of them; N and npoint then come from the two offset arrays and the indices written are
+// GLOBAL rows.  The template is picked from the largest cloud, a smaller cloud leaves the slots past its size masked
+// (md = -1), exactly as the dense kernel does for N < BLOCK * P; the arithmetic of a step is the same code.
+template <int BLOCK, int P, bool RAGGED>
 __global__ __launch_bounds__(BLOCK) void fps_reg_kernel(const float *__restrict__ xyz, int N, int npoint,
-                                                         int64_t *__restrict__ out)
+                                                         int64_t *__restrict__ out,
+                                                         const int64_t *__restrict__ seg_in,
+                                                         const int64_t *__restrict__ seg_out, int64_t M)
 {
     constexpr int NW = BLOCK / kWave;
     constexpr int H = P / 2;
@@ -102,6 +109,17 @@ __global__ __launch_bounds__(BLOCK) void fps_reg_kernel(const float *__restrict_
     const int wave = t / kWave;
     const float *p = xyz + (size_t)b * N * 3;
     int64_t *o = out + (size_t)b * npoint;
+    int64_t base = 0;
+    if (RAGGED) {
+        base = seg_in[b];
+        const int64_t cnt = seg_in[b + 1] - base, quota = seg_out[b + 1] - seg_out[b];
+        // (workgroup-uniform exit, in front of every barrier: an empty cloud, a zero quota, offsets outside the tensor)
+        if (cnt <= 0 || quota <= 0 || base < 0 || base + cnt > M || cnt > (int64_t)BLOCK * P) return;
+        N = (int)cnt;
+        npoint = (int)(quota < cnt ? quota : cnt);
+        p = xyz + (size_t)base * 3;
+        o = out + seg_out[b];
+    }
 
     f2 px[H], py[H], pz[H], md[H];  // element e of pair h is slot k = 2h + e
 #pragma unroll
@@ -114,7 +132,7 @@ __global__ __launch_bounds__(BLOCK) void fps_reg_kernel(const float *__restrict_
         md[k / 2][k & 1] = ok ? 1e10f : -1.0f;  // -1 never wins: every real point has min-distance >= 0
     }
 
-    if (t == 0 && npoint > 0) o[0] = 0;
+    if (t == 0 && npoint > 0) o[0] = base;
     float lx = p[0], ly = p[1], lz = p[2];
 
     for (int it = 1; it < npoint; ++it) {
@@ -188,15 +206,18 @@ __global__ __launch_bounds__(BLOCK) void fps_reg_kernel(const float *__restrict_
             ly = oy;
             lz = oz;
         }
-        if (t == 0) o[it] = last;
+        if (t == 0) o[it] = RAGGED ? base + last : (int64_t)last;
     }
 }
 
 // Any N: running min-distance kept in caller scratch (B*N floats), cloud re-read from L2 each step.
-template <int BLOCK>
+// RAGGED: as above; scratch is then M floats, a cloud's slice starts at its first row.
+template <int BLOCK, bool RAGGED>
 __global__ __launch_bounds__(BLOCK) void fps_generic_kernel(const float *__restrict__ xyz, int N, int npoint,
                                                              float *__restrict__ scratch,
-                                                             int64_t *__restrict__ out)
+                                                             int64_t *__restrict__ out,
+                                                             const int64_t *__restrict__ seg_in,
+                                                             const int64_t *__restrict__ seg_out, int64_t M)
 {
     constexpr int NW = BLOCK / kWave;
     __shared__ float s_v[2][NW];
@@ -208,9 +229,20 @@ __global__ __launch_bounds__(BLOCK) void fps_generic_kernel(const float *__restr
     const float *p = xyz + (size_t)b * N * 3;
     float *md = scratch + (size_t)b * N;
     int64_t *o = out + (size_t)b * npoint;
+    int64_t base = 0;
+    if (RAGGED) {
+        base = seg_in[b];
+        const int64_t cnt = seg_in[b + 1] - base, quota = seg_out[b + 1] - seg_out[b];
+        if (cnt <= 0 || quota <= 0 || base < 0 || base + cnt > M || cnt * 3 > INT32_MAX) return;  // workgroup-uniform
+        N = (int)cnt;
+        npoint = (int)(quota < cnt ? quota : cnt);
+        p = xyz + (size_t)base * 3;
+        md = scratch + base;
+        o = out + seg_out[b];
+    }
 
     for (int j = t; j < N; j += BLOCK) md[j] = 1e10f;
-    if (t == 0 && npoint > 0) o[0] = 0;
+    if (t == 0 && npoint > 0) o[0] = base;
     float lx = p[0], ly = p[1], lz = p[2];
 
     for (int it = 1; it < npoint; ++it) {
@@ -250,14 +282,23 @@ __global__ __launch_bounds__(BLOCK) void fps_generic_kernel(const float *__restr
         lx = p[(size_t)last * 3 + 0];
         ly = p[(size_t)last * 3 + 1];
         lz = p[(size_t)last * 3 + 2];
-        if (t == 0) o[it] = last;
+        if (t == 0) o[it] = RAGGED ? base + last : (int64_t)last;
     }
 }
 
 template <int BLOCK, int P>
 static void launch_reg(const float *xyz, int B, int N, int npoint, int64_t *out, hipStream_t s)
 {
-    hipLaunchKernelGGL((fps_reg_kernel<BLOCK, P>), dim3(B), dim3(BLOCK), 0, s, xyz, N, npoint, out);
+    hipLaunchKernelGGL((fps_reg_kernel<BLOCK, P, false>), dim3(B), dim3(BLOCK), 0, s, xyz, N, npoint, out, nullptr,
+                       nullptr, (int64_t)0);
+}
+
+template <int BLOCK, int P>
+static void launch_reg_ragged(const float *pos, const int64_t *seg_in, const int64_t *seg_out, int clouds, int64_t M,
+                              int64_t *out, hipStream_t s)
+{
+    hipLaunchKernelGGL((fps_reg_kernel<BLOCK, P, true>), dim3(clouds), dim3(BLOCK), 0, s, pos, 0, 0, out, seg_in,
+                       seg_out, M);
 }
 
 }  // namespace tp3d
@@ -284,8 +325,35 @@ TP3D_EXPORT int tp3d_fps_f32(const float *xyz, int B, int N, int npoint, float *
     else if (N <= TP3D_FPS_MAX_REG_POINTS) launch_reg<1024, 32>(xyz, B, N, npoint, out_idx, s);
     else {
         if (!scratch) return TP3D_E_BADARG;
-        hipLaunchKernelGGL((fps_generic_kernel<1024>), dim3(B), dim3(1024), 0, s, xyz, N, npoint, scratch,
-                           out_idx);
+        hipLaunchKernelGGL((fps_generic_kernel<1024, false>), dim3(B), dim3(1024), 0, s, xyz, N, npoint, scratch,
+                           out_idx, nullptr, nullptr, (int64_t)0);
+    }
+    return check_launch();
+}
+
+// Reference contract: torch_points3d/core/spatial_ops/sampling.py:53-63 (FPSSampler.sample -> torch_geometric fps).
+TP3D_EXPORT int tp3d_fps_ragged_f32(const float *pos, const int64_t *seg_in, const int64_t *seg_out, int64_t M,
+                                    int clouds, int max_cloud_points, float *scratch, int64_t *out_idx, void *stream)
+{
+    using namespace tp3d;
+    if (M < 0 || clouds < 0 || max_cloud_points < 0 || max_cloud_points > M) return TP3D_E_BADARG;
+    if (clouds == 0 || M == 0 || max_cloud_points == 0) return TP3D_OK;
+    if (!pos || !seg_in || !seg_out || !out_idx) return TP3D_E_BADARG;
+    if ((int64_t)max_cloud_points * 3 > INT32_MAX) return TP3D_E_TOOBIG;
+    hipStream_t s = (hipStream_t)stream;
+    const int N = max_cloud_points;  // the thresholds of tp3d_fps_f32, on the largest cloud
+    if (N <= 128) launch_reg_ragged<64, 2>(pos, seg_in, seg_out, clouds, M, out_idx, s);
+    else if (N <= 512) launch_reg_ragged<256, 2>(pos, seg_in, seg_out, clouds, M, out_idx, s);
+    else if (N <= 1024) launch_reg_ragged<256, 4>(pos, seg_in, seg_out, clouds, M, out_idx, s);
+    else if (N <= 2048) launch_reg_ragged<512, 4>(pos, seg_in, seg_out, clouds, M, out_idx, s);
+    else if (N <= 4096) launch_reg_ragged<512, 8>(pos, seg_in, seg_out, clouds, M, out_idx, s);
+    else if (N <= 8192) launch_reg_ragged<512, 16>(pos, seg_in, seg_out, clouds, M, out_idx, s);
+    else if (N <= 16384) launch_reg_ragged<512, 32>(pos, seg_in, seg_out, clouds, M, out_idx, s);
+    else if (N <= TP3D_FPS_MAX_REG_POINTS) launch_reg_ragged<1024, 32>(pos, seg_in, seg_out, clouds, M, out_idx, s);
+    else {
+        if (!scratch) return TP3D_E_BADARG;
+        hipLaunchKernelGGL((fps_generic_kernel<1024, true>), dim3(clouds), dim3(1024), 0, s, pos, 0, 0, scratch,
+                           out_idx, seg_in, seg_out, M);
     }
     return check_launch();
 }

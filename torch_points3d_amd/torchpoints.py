@@ -18,6 +18,7 @@ import torch
 from . import _lib
 
 __all__ = ["furthest_point_sample", "ball_query", "three_nn", "three_interpolate", "grouping_operation"]
+# (message-passing side: fps_quota, fps_ragged, radius_edges, pointconv_rows, segment_max -- further down)
 
 
 def _dev(*tensors):
@@ -62,6 +63,195 @@ def furthest_point_sample(xyz, npoint):
         _lib.call("tp3d_fps_f32", _lib.ptr(xyz), B, N, int(npoint), _lib.ptr(scratch), _lib.ptr(out),
                   _lib.stream_ptr(dev))
     return out
+
+
+def fps_quota(counts, ratio):
+    """Points furthest-point sampling keeps of clouds with `counts` points: ceil(float32(n) * float32(ratio)), clamped
+    to [0, n].  Host arithmetic on a CPU int64 tensor (or a list); returns a CPU int64 tensor.
+
+    This is torch_cluster 1.5.9's rule AS RECALLED (`deg.float() * ratio` then `.ceil()`): its source is not part of
+    the reference tree, so the rounding is unverified.  The reference's only pin, test/test_fps.py:35-42 (5 points,
+    ratio 3/5 -> 3 indices), holds under it."""
+    n = torch.as_tensor(counts, dtype=torch.int64, device="cpu")
+    q = torch.ceil(n.to(torch.float32) * torch.tensor(float(ratio), dtype=torch.float32)).to(torch.int64)
+    return torch.minimum(torch.clamp(q, min=0), n)
+
+
+def fps_ragged(pos, batch, ratio=None, counts=None):
+    """Furthest-point sampling of every cloud of a ragged batch: pos (M,3), sorted `batch` (M) (None = one cloud) ->
+    int64 GLOBAL row indices, cloud after cloud, each in selection order (torch_geometric's `fps(pos, batch, ratio)`,
+    reference core/spatial_ops/sampling.py:53-63).
+
+    Every cloud starts at its FIRST row (deterministic; torch_cluster draws a random start by default) and keeps
+    fps_quota(n_b, ratio) points, or counts[b] when `counts` (one int per cloud) is given instead of a ratio.
+    Host reads: the cloud sizes (one read of the segment table, remembered per batch tensor by _segments)."""
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError("pos must be (M, 3), got %s" % (tuple(pos.shape),))
+    if (ratio is None) == (counts is None):
+        raise ValueError("give exactly one of ratio and counts")
+    dev = _dev(pos, batch)
+    pos = _f32(pos)
+    M = pos.shape[0]
+    bx = torch.zeros(M, dtype=torch.int64, device=dev) if batch is None else _i64(batch)
+    if bx.numel() != M:
+        raise ValueError("batch must have one entry per point")
+    seg_in, nclouds, nmax = _segments(bx)
+    sizes = _segment_sizes(bx, seg_in)
+    quota = fps_quota(sizes, ratio) if counts is None else torch.as_tensor(counts, dtype=torch.int64, device="cpu").reshape(-1)
+    if quota.numel() != nclouds:
+        raise ValueError("counts must have one entry per cloud (%d), got %d" % (nclouds, quota.numel()))
+    if bool((quota > sizes).any()) or bool((quota < 0).any()):
+        raise ValueError("cannot sample more points than a cloud has")
+    seg_out_host = torch.zeros(nclouds + 1, dtype=torch.int64)
+    seg_out_host[1:] = torch.cumsum(quota, 0)
+    total = int(seg_out_host[-1])
+    out = torch.empty(total, dtype=torch.int64, device=dev)
+    if total == 0:
+        return out
+    seg_out = seg_out_host.to(dev)
+    scratch = torch.empty(M, dtype=torch.float32, device=dev) if nmax > 32768 else None  # TP3D_FPS_MAX_REG_POINTS
+    with _lib.on_device(dev):
+        _lib.call("tp3d_fps_ragged_f32", _lib.ptr(pos), _lib.ptr(seg_in), _lib.ptr(seg_out), M, nclouds, nmax,
+                  _lib.ptr(scratch), _lib.ptr(out), _lib.stream_ptr(dev))
+    return out
+
+
+_size_cache = {}
+
+
+def _segment_sizes(bx, seg):
+    """cloud sizes as a CPU int64 tensor (one host read, remembered with the batch tensor like _segments)"""
+    key = (bx.data_ptr(), bx.numel(), bx._version, bx.device.index)
+    hit = _size_cache.get(key)
+    if hit is not None and hit[0]() is bx:
+        return hit[1]
+    sizes = (seg[1:] - seg[:-1]).cpu()
+    if len(_size_cache) > 64:
+        _size_cache.clear()
+    _size_cache[key] = (weakref.ref(bx), sizes)
+    return sizes
+
+
+def table_edges(table):
+    """The -1 padded neighbour table (Nq, max_num) of ball_query(mode="partial_dense") as CSR edges:
+    edge_start (Nq+1) int64 (exclusive scan of the hits per query) and col (E) int64 (support rows, row-major, a
+    query's hits in the table's order).  One host read: E = edge_start[Nq] sizes `col` (torch_cluster's `radius`, which
+    the reference calls, waits for its edge count in the same way)."""
+    dev = _dev(table)
+    table = _i64(table)
+    Nq, W = table.shape
+    edge_start = torch.empty(Nq + 1, dtype=torch.int64, device=dev)
+    st = _lib.stream_ptr(dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_table_edge_start_i64", _lib.ptr(table), Nq, W, _lib.ptr(edge_start), st)
+        E = int(edge_start[Nq])  # the one host read
+        col = torch.empty(E, dtype=torch.int64, device=dev)
+        _lib.call("tp3d_table_edge_col_i64", _lib.ptr(table), _lib.ptr(edge_start), Nq, W, E, _lib.ptr(col), st)
+    return edge_start, col
+
+
+def radius_edges(radius, max_num_neighbors, x, y, batch_x=None, batch_y=None):
+    """Radius search as CSR edges (edge_start (Nq+1), col (E)): for query i of y the first max_num_neighbors support
+    rows of x, in ascending row order, with squared distance < radius^2 inside the query's cloud.  One host read (E)."""
+    dev = _dev(x, y)
+    bx = torch.zeros(x.shape[0], dtype=torch.int64, device=dev) if batch_x is None else batch_x
+    by = torch.zeros(y.shape[0], dtype=torch.int64, device=dev) if batch_y is None else batch_y
+    table, _ = ball_query(radius, int(max_num_neighbors), x, y, mode="partial_dense", batch_x=bx, batch_y=by)
+    return table_edges(table)
+
+
+class _PointConvRows(torch.autograd.Function):
+    """rows (E, ld) = [ x[col] | pos_s[col] - pos_q[query of the edge] | 0 ];  differentiable wrt x."""
+
+    @staticmethod
+    def forward(ctx, x, pos_s, pos_q, edge_start, col, ld):
+        dev = pos_s.device
+        M, Nq, E = pos_s.shape[0], pos_q.shape[0], col.shape[0]
+        C = 0 if x is None else x.shape[1]
+        xf = None if x is None else _f32(x)
+        out = torch.empty((E, ld), dtype=torch.float32, device=dev)
+        with _lib.on_device(dev):
+            _lib.call("tp3d_pointconv_rows_f32", _lib.ptr(xf), _lib.ptr(pos_s), _lib.ptr(pos_q), _lib.ptr(edge_start),
+                      _lib.ptr(col), Nq, M, E, C, ld, _lib.ptr(out), _lib.stream_ptr(dev))
+        ctx.save_for_backward(col)
+        ctx.cfg = (M, C, ld)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (col,) = ctx.saved_tensors
+        M, C, ld = ctx.cfg
+        dx = None
+        if C and ctx.needs_input_grad[0]:
+            g = g.float().contiguous()
+            dev = g.device
+            E = col.shape[0]
+            dx = torch.empty((M, C), dtype=torch.float32, device=dev)
+            if E == 0:
+                dx.zero_()
+            else:
+                ws, nbytes = _lib.scatter_workspace(1, E, M, False, dev)
+                with _lib.on_device(dev):
+                    _lib.call("tp3d_rows_scatter_bwd_f32", _lib.ptr(g), _lib.ptr(col), None, 1, E, 1, M, ld, 0, C,
+                              _lib.ptr(dx), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+        return dx, None, None, None, None, None
+
+
+def pointconv_rows(x, pos_s, pos_q, edge_start, col, ld=None):
+    """The message rows of PointConv, cat([x_j, pos_j - pos_i]) per edge: x (M,C) or None, pos_s (M,3), pos_q (Nq,3),
+    CSR edges -> (E, ld) float32, ld >= C+3 (default: C+3 rounded up to a multiple of 4, zero padded)."""
+    dev = _dev(pos_s, pos_q, edge_start, col, x)
+    C = 0 if x is None else x.shape[1]
+    ld = ((C + 3 + 3) & ~3) if ld is None else int(ld)
+    if ld < C + 3:
+        raise ValueError("ld must be at least C + 3")
+    if edge_start.numel() != pos_q.shape[0] + 1:
+        raise ValueError("edge_start must have one entry per query plus one")
+    return _PointConvRows.apply(x, _f32(pos_s), _f32(pos_q), _i64(edge_start), _i64(col), ld)
+
+
+class _SegmentMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rows, seg, C):
+        dev = rows.device
+        rows = rows.detach().float().contiguous()
+        E, ld = rows.shape
+        S = seg.numel() - 1
+        out = torch.empty((S, C), dtype=torch.float32, device=dev)
+        arg = torch.empty((S, C), dtype=torch.int64, device=dev)
+        with _lib.on_device(dev):
+            _lib.call("tp3d_segment_max_fwd_f32", _lib.ptr(rows), _lib.ptr(seg), S, E, C, ld, _lib.ptr(out),
+                      _lib.ptr(arg), _lib.stream_ptr(dev))
+        ctx.save_for_backward(arg, seg)
+        ctx.cfg = (E, ld, C)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, g, _garg):
+        arg, seg = ctx.saved_tensors
+        E, ld, C = ctx.cfg
+        g = g.float().contiguous()
+        dev = g.device
+        d_rows = torch.empty((E, ld), dtype=torch.float32, device=dev)
+        with _lib.on_device(dev):
+            _lib.call("tp3d_segment_max_bwd_f32", _lib.ptr(g), _lib.ptr(arg), _lib.ptr(seg), seg.numel() - 1, E, C, ld,
+                      _lib.ptr(d_rows), _lib.stream_ptr(dev))
+        return d_rows, None, None
+
+
+def segment_max(rows, seg, C=None, return_argmax=False):
+    """out (S, C) = max over the rows seg[s] .. seg[s+1]) of rows (E, ld), columns [0, C) (default: all); seg (S+1)
+    int64 ascending from 0 to E.  The first maximum wins; an empty segment gives 0.0 (argmax -1).  Differentiable wrt
+    rows (the gradient goes to the winning row)."""
+    dev = _dev(rows, seg)
+    if rows.dim() != 2 or seg.dim() != 1 or seg.numel() < 1:
+        raise ValueError("rows must be (E, ld) and seg (S + 1,)")
+    C = rows.shape[1] if C is None else int(C)
+    if C > rows.shape[1]:
+        raise ValueError("C exceeds the row length")
+    out, arg = _SegmentMax.apply(rows, _i64(seg), C)
+    return (out, arg) if return_argmax else out
 
 
 def ball_query(radius, nsample, x, y, mode="dense", batch_x=None, batch_y=None, sort=False):
