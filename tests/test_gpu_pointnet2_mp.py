@@ -42,7 +42,8 @@ def _batch_of(sizes):
 
 
 # ---------------------------------------------------------------------------------------------------- ragged FPS
-RAGGED_SIZES = [65, 1, 4099, 2, 0, 63, 1025, 64, 257]  # id 4 has no point; every register template up to 8192
+RAGGED_SIZES = [65, 1, 4099, 2, 0, 63, 1025, 64, 257]  # id 4 has no point.  ONE template serves the whole batch, picked from
+# the largest cloud: <512,16> here; the others are tests/test_gpu_pointnet2_mp_sizes.py's
 
 
 @pytest.fixture(scope="module")

@@ -144,3 +144,86 @@ def test_cpu_statement_of_the_kernels():
     vals = torch.tensor([[1.0], [3.0], [3.0], [2.0], [0.5]])
     out, arg = ref.segment_max(vals, es)
     assert out.reshape(-1).tolist() == [3.0, 0.0, 3.0] and arg.reshape(-1).tolist() == [1, -1, 2]
+
+
+# ------------------------------------------------------------------------------ the torch mirror of the modules, pinned
+# tests/pointnet2_mp_ref.py restates PointConv / SAModule / GlobalBaseModule / FPModule / PointNet2MP in plain torch so
+# that GPU tests can evaluate them in float64 at widths no fixture can hold.  Before it is trusted there, its float64
+# run has to reproduce what the REFERENCE's own classes computed in float64 (the fixture's f64/* arrays) and the stored
+# gradients.  The bar is the one test_fixture_is_self_consistent states for the fixture's own float32-vs-float64
+# distance, 1e-5 * max(1, scale): the float64 arrays are met to rounding, the stored gradients are float32 ones.
+def _within(got, want, what):
+    want = torch.as_tensor(want).double()
+    scale = max(1.0, float(want.abs().max()))
+    d = float((got.detach().double() - want).abs().max())
+    print("mirror vs fixture, %s: max distance %.3e (bar %.1e)" % (what, d, 1e-5 * scale))
+    assert got.shape == want.shape and d <= 1e-5 * scale, (what, d, scale)
+
+
+def _gold_plan(oracle, gold):
+    down, up = ref.GOLD_CFG["down_conv"], ref.GOLD_CFG["up_conv"]
+    plan = ref.search_plan(oracle, gold["pos"], gold["batch"], down["ratios"], down["radius"], down["radius_num_points"],
+                           up["up_k"])
+    for i in range(2):  # the oracle's searches ARE the fixture's
+        assert torch.equal(plan["idx"][i], gold["sa%d/idx" % (i + 1)])
+        assert torch.equal(plan["edges"][i][0][0], gold["edges/sa%d/edge_start" % (i + 1)])
+        assert torch.equal(plan["edges"][i][0][1], gold["edges/sa%d/col" % (i + 1)])
+    assert [tuple(t.shape) for t in plan["knn"]] == [(21, 1), (81, 3), (321, 3)]
+    return plan
+
+
+def test_float64_mirror_reproduces_the_fixture(oracle, gold):
+    sd = {k[3:]: v for k, v in gold.items() if k.startswith("sd/")}
+    net = ref.PointNet2MP.from_state_dict(sd, torch.float64)
+    assert net.levels == 2 and list(net.state_dict().keys()) == list(sd.keys())
+    x = gold["x"].double().requires_grad_(True)
+    rec = net(x, gold["pos"].double(), gold["batch"], _gold_plan(oracle, gold))
+    for k in ("sa1", "sa2", "glob", "fp0", "fp1", "fp2", "out"):
+        _within(rec[k], gold["f64/" + k + "/x"], k)
+    (rec["out"] * gold["cot"].double()).sum().backward()
+    _within(x.grad, gold["grad/x"], "grad x")
+    checked = 0
+    for name, p in net.named_parameters():
+        want = gold.get("pgrad/" + name)
+        assert want is not None and p.grad is not None, name
+        _within(p.grad, want, "grad " + name)
+        checked += 1
+    assert checked > 50
+    # the float32 run of the same classes lies as close to the float64 arrays as the fixture's own float32 pass does
+    net32 = ref.PointNet2MP.from_state_dict(sd, torch.float32)
+    rec32 = net32(gold["x"], gold["pos"], gold["batch"], _gold_plan(oracle, gold))
+    for k in ("sa1", "sa2", "glob", "fp0", "fp1", "fp2", "out"):
+        _within(rec32[k], gold["f64/" + k + "/x"], k + " (float32 mirror)")
+
+
+def test_float64_mirror_reproduces_the_two_scale_module(gold):
+    sd = {k[len("ms/sd/"):]: v for k, v in gold.items() if k.startswith("ms/sd/")}
+    sa = ref.SAModule.from_state_dict(sd, torch.float64)
+    edges = [(gold["ms/edges%d/edge_start" % s], gold["ms/edges%d/col" % s]) for s in range(2)]
+    x = gold["x"].double().requires_grad_(True)
+    out = sa(x, gold["pos"].double(), gold["ms/idx"], edges)
+    _within(out, gold["ms/f64/x"], "two-scale SAModule")
+    (out * gold["ms/cot"].double()).sum().backward()
+    _within(x.grad, gold["ms/grad_x"], "two-scale SAModule grad x")
+
+
+def test_mirror_pieces_by_hand():
+    """a query without an edge gives 0.0 and its rows are absent from BatchNorm; the blend skips -1 slots; modules build
+    from a state_dict alone"""
+    from torch_points3d_amd.pointnet2_mp import FPModule, GlobalBaseModule, SAModule
+    torch.manual_seed(0)
+    prod = SAModule(ratio=0.5, radius=1.0, radius_num_point=4, down_conv_nn=[2 + 3, 8, 6])
+    sa = ref.SAModule.from_state_dict(prod.state_dict(), torch.float64)
+    pos = torch.rand(6, 3).double()
+    x = torch.randn(6, 2).double()
+    es, col = torch.tensor([0, 2, 2, 5]), torch.tensor([0, 3, 1, 2, 5])
+    out = sa._conv(x, (pos, torch.rand(3, 3).double()), (es, col))
+    assert out.shape == (3, 6) and not bool(out[1].any()) and bool(out[0].any())
+    assert int(sa._conv.local_nn[0][1].batch_norm.num_batches_tracked) == 1
+    w = ref.knn_blend(torch.tensor([[1.0], [3.0], [100.0]]), torch.tensor([[1.0, 0, 0], [-1.0, 0, 0], [9.0, 9, 9]]),
+                      torch.zeros(1, 3), torch.tensor([[0, 1, -1]]))
+    assert w.tolist() == [[2.0]]
+    glob = ref.GlobalBaseModule.from_state_dict(GlobalBaseModule(nn=[5, 7]).state_dict())
+    assert glob(x, pos, torch.tensor([0, 0, 0, 2, 2, 2])).shape == (3, 7)
+    fp = ref.FPModule.from_state_dict(FPModule(up_k=1, up_conv_nn=[4, 3]).state_dict())
+    assert fp.nn[0][0].bias is None and fp.nn[0][0].in_features == 4
