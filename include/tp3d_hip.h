@@ -35,7 +35,7 @@ extern "C" {
 #define TP3D_E_UNSORTED (-3) /* reserved: batch vector not sorted (checked by the host wrapper) */
 #define TP3D_E_TOOBIG (-4)   /* size exceeds what the kernel's index arithmetic supports */
 
-#define TP3D_ABI_VERSION 38
+#define TP3D_ABI_VERSION 39
 
 int tp3d_abi_version(void);
 const char *tp3d_strerror(int code);
@@ -490,6 +490,27 @@ int tp3d_nbr_maxpool_fwd_f32(const float *x, const int64_t *neighbors, int64_t N
 int tp3d_nbr_maxpool_bwd_f32(const float *grad_out, const int32_t *argmax, const int64_t *neighbors, int64_t Nq,
                              int64_t M, int Mn, int C, float *d_x, void *inverse, size_t inverse_bytes,
                              int inverse_ready, void *stream);
+
+/* PosPool position pooling of PPNet (modules/PPNet/ops.py:44-109), csrc/pospool.hip:
+ *   rel = (support[neighbors[q,n]] - query[q]) / radius
+ *   out[q, c] = sum over n of geo(rel, c) * features[neighbors[q,n], c]     a shadow neighbour (-1 or >= M) adds nothing
+ * embedding 0 (xyz, C % 3 == 0): geo = rel[c / (C/3)].  embedding 1 (sin_cos, C % 6 == 0 with F = C/6, or C == 9 with
+ * F = 1): c = axis * 2F + t, geo = sin(100 rel[axis] / dim_mat[t]) for t < F, cos(100 rel[axis] / dim_mat[t - F])
+ * otherwise; C == 9: channels 6..8 are rel itself.  dim_mat: device (F,) table 1000^(j/F) (unused for xyz, may be NULL).
+ * reduction 0 sum, 1 avg: out / (n_q + 1e-5), n_q = slots of row q whose index, shadows mapped to M, is < *padding;
+ * padding: DEVICE int64, the maximum of the table with its shadows mapped to M (tp3d_pospool_padding_i64) -- what the
+ * reference's torch.max(neighbors) returns after its gather has rewritten -1 to M.
+ * counts (Nq) or NULL: n_q + 1e-5 as float, what the backward divides by.
+ * Backward: d_features (M,C) overwritten (positions carry no gradient); atomic-free and bit-reproducible through the
+ * inverted neighbour table, inverse / inverse_ready as for tp3d_kpconv_bwd_features_f32; counts may be NULL for sum. */
+int tp3d_pospool_padding_i64(const int64_t *neighbors, int64_t slots, int64_t M, int64_t *padding, void *stream);
+int tp3d_pospool_fwd_f32(const float *query, const float *support, const int64_t *neighbors, const float *features,
+                         const int64_t *padding, const float *dim_mat, int64_t Nq, int64_t M, int Mn, int C, float radius,
+                         int embedding, int reduction, float *out, float *counts, void *stream);
+int tp3d_pospool_bwd_f32(const float *query, const float *support, const int64_t *neighbors, const float *grad_out,
+                         const float *counts, const float *dim_mat, int64_t Nq, int64_t M, int Mn, int C, float radius,
+                         int embedding, int reduction, float *d_features, void *inverse, size_t inverse_bytes,
+                         int inverse_ready, void *stream);
 
 /* =====================================================================================================
  * Message-passing PointNet++ (modules/pointnet2/message_passing.py:9-31 SAModule = FPSSampler +

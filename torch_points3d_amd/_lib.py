@@ -56,6 +56,9 @@ SIGNATURES = {
     "tp3d_knn_interpolate_fwd_f32": [_p, _p, _p, _p, _l, _i, _i, _i, _i, _p, _p, _p],
     "tp3d_nbr_maxpool_fwd_f32": [_p, _p, _l, _l, _i, _i, _p, _p, _p],
     "tp3d_nbr_maxpool_bwd_f32": [_p, _p, _p, _l, _l, _i, _i, _p, _p, ctypes.c_size_t, _i, _p],
+    "tp3d_pospool_padding_i64": [_p, _l, _l, _p, _p],
+    "tp3d_pospool_fwd_f32": [_p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _f, _i, _i, _p, _p, _p],
+    "tp3d_pospool_bwd_f32": [_p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _f, _i, _i, _p, _p, ctypes.c_size_t, _i, _p],
     "tp3d_voxel_bounds_f32": [_p, _p, _l, _f, _p, _p],
     "tp3d_voxel_cluster_f32": [_p, _p, _l, _f, _p, _p, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
     "tp3d_cluster_mean_f32": [_p, _p, _p, _l, _i, _p, _p],
@@ -110,7 +113,7 @@ MISC = {
     "tp3d_voxel_workspace_bytes": (_z, [_l]),
     "tp3d_ball_query_workspace_bytes": (_z, [_i, _l, _i]),
 }
-ABI_VERSION = 38
+ABI_VERSION = 39
 
 _handle = None
 

@@ -96,6 +96,53 @@ class RadiusNeighbourFinder(object):
         return idx
 
 
+def block_query_data(block, data, precomputed=None):
+    """`(query_data, q_pos, idx_neighboors)` of a partial-dense block (reference modules/KPConv/blocks.py:66-85, the same
+    lines in modules/PPNet/blocks.py): the `precomputed` entry of this block, or the block's sampler (strided) and
+    neighbour search.  `block` has `is_strided`, `sampler` and `neighbour_finder`; `data.block_idx` is set when missing."""
+    if not hasattr(data, "block_idx"):
+        data.block_idx = 0
+    if precomputed:
+        query_data = _copy(precomputed[data.block_idx])  # (the caller's table is left untouched)
+        return query_data, query_data.pos, query_data.idx_neighboors
+    if block.is_strided:
+        sample_in = _copy(data)
+        if isinstance(block.sampler, GridSampling3D):
+            sample_in.x = None  # the block overwrites query_data.x: averaging the features is wasted work
+        query_data = block.sampler(sample_in)
+    else:
+        query_data = _copy(data)
+    q_pos = query_data.pos
+    idx_neighboors = block.neighbour_finder(data.pos, q_pos, batch_x=data.batch, batch_y=query_data.batch)
+    query_data.idx_neighboors = idx_neighboors
+    return query_data, q_pos, idx_neighboors
+
+
+def bn_act_rows(x, bn, activation, fused):
+    """BatchNorm (or none) and activation on rows: statistics + affine + activation in two kernels when the modules have
+    that shape and `fused`, else the modules themselves."""
+    bn1d = _fused._bn1d_of(bn) if (fused and bn is not None and x.is_cuda) else None
+    slope = _fused._slope_of(activation)
+    if bn1d is not None and slope is not None:
+        return _fused.bn_act(x, bn1d, slope)
+    if bn:
+        x = bn(x)
+    return activation(x)
+
+
+def strided_shortcut(x, idx, fused):
+    """Shortcut of a strided ResnetBBlock (reference modules/KPConv/blocks.py:206-210, modules/PPNet/blocks.py:277-281):
+    max over each query's neighbours of the support rows, a shadow neighbour contributing the zero row."""
+    if fused and x.is_cuda:
+        return _fused.nbr_maxpool(x, idx)
+    padded = torch.cat([x, torch.zeros_like(x[:1, :])], dim=0)  # shadow feature row
+    idx = torch.where(idx < 0, torch.full_like(idx, x.shape[0]), idx)
+    # (index_select, not padded[idx]: the backward of 2-D advanced indexing runs ATen's
+    #  indexing_backward_kernel_small_stride, which reads past the end of its index buffer on this ROCm build
+    #  -- tests/guard/ found it)
+    return torch.index_select(padded, 0, idx.reshape(-1)).view(idx.shape[0], idx.shape[1], -1).max(dim=1)[0]
+
+
 class SimpleBlock(nn.Module):
     """KPConv -> BatchNorm -> LeakyReLU(0.1); strided when prev_grid_size != grid_size.  deformable=True builds a
     `KPConvDeformableLayer` and searches with the wider radius of the reference (5.0 * sigma * prev_grid_size,
@@ -125,32 +172,9 @@ class SimpleBlock(nn.Module):
         self.sampler = (sampler if sampler is not None else GridSampling3D(grid_size)) if self.is_strided else None
 
     def forward(self, data, precomputed=None, **kwargs):
-        if not hasattr(data, "block_idx"):
-            data.block_idx = 0
-        if precomputed:
-            query_data = _copy(precomputed[data.block_idx])  # (the caller's table is left untouched)
-            idx_neighboors, q_pos = query_data.idx_neighboors, query_data.pos
-        else:
-            if self.is_strided:
-                sample_in = _copy(data)
-                if isinstance(self.sampler, GridSampling3D):
-                    sample_in.x = None  # the block overwrites query_data.x below: averaging the features is wasted work
-                query_data = self.sampler(sample_in)
-            else:
-                query_data = _copy(data)
-            q_pos = query_data.pos
-            idx_neighboors = self.neighbour_finder(data.pos, q_pos, batch_x=data.batch, batch_y=query_data.batch)
-            query_data.idx_neighboors = idx_neighboors
+        query_data, q_pos, idx_neighboors = block_query_data(self, data, precomputed)
         x = self.kp_conv(q_pos, data.pos, idx_neighboors, data.x)
-        bn1d = _fused._bn1d_of(self.bn) if (self.fused and self.bn is not None and x.is_cuda) else None
-        slope = _fused._slope_of(self.activation)
-        if bn1d is not None and slope is not None:
-            x = _fused.bn_act(x, bn1d, slope)  # BatchNorm statistics + affine + activation: two kernels
-        else:
-            if self.bn:
-                x = self.bn(x)
-            x = self.activation(x)
-        query_data.x = x
+        query_data.x = bn_act_rows(x, self.bn, self.activation, self.fused)
         query_data.block_idx = data.block_idx + 1
         return query_data
 
@@ -205,16 +229,7 @@ class ResnetBBlock(nn.Module):
         if self.has_bottleneck:
             output.x = seq(self.unary_2, output.x)
         if self.is_strided:
-            idx = output.idx_neighboors
-            if self.fused and shortcut_x.is_cuda:
-                shortcut_x = _fused.nbr_maxpool(shortcut_x, idx)
-            else:
-                padded = torch.cat([shortcut_x, torch.zeros_like(shortcut_x[:1, :])], dim=0)  # shadow feature row
-                idx = torch.where(idx < 0, torch.full_like(idx, shortcut_x.shape[0]), idx)
-                # (index_select, not padded[idx]: the backward of 2-D advanced indexing runs ATen's
-                #  indexing_backward_kernel_small_stride, which reads past the end of its index buffer on this ROCm build
-                #  -- tests/guard/ found it)
-                shortcut_x = torch.index_select(padded, 0, idx.reshape(-1)).view(idx.shape[0], idx.shape[1], -1).max(dim=1)[0]
+            shortcut_x = strided_shortcut(shortcut_x, output.idx_neighboors, self.fused)
         output.x = output.x + seq(self.shortcut_op, shortcut_x)
         return output
 
