@@ -549,6 +549,34 @@ int tp3d_segment_max_bwd_f32(const float *dout, const int64_t *argmax, const int
                              int ld, float *d_rows, void *stream);
 
 /* =====================================================================================================
+ * Message-passing RSConv (modules/RSConv/message_passing.py:10-60 Convolution, RSConvDown): the relation rows of
+ * the edges and the fused "gather x weight -> max" aggregation over the same CSR edge list (csrc/rsconv_mp.hip).
+ * ===================================================================================================== */
+
+/* relation vector h_ij of Convolution.message                        [modules/RSConv/message_passing.py:35-38]
+ *   for edge e of query i with support row j = col[e], d = pos_q[i] - pos_s[j] (query minus support):
+ *   out[e, :] = [ sqrt(dx^2 + dy^2 + dz^2) | d | pos_q[i] | pos_s[j] | 0 .. ];  out (E, ld), ld >= 10, columns past
+ *   10 are written as zeros.  A col outside [0, M) gives a zero row.  No gradient (positions carry none). */
+int tp3d_rsconv_relation_rows_f32(const float *pos_s, const float *pos_q, const int64_t *edge_start, const int64_t *col,
+                                  int64_t Nq, int64_t M, int64_t E, int ld, float *out, void *stream);
+
+/* aggr="max" of the messages M_ij * x_j                             [modules/RSConv/message_passing.py:42-44]
+ *   w (E, ldw), x (M, ldx), C <= ldw, ldx -> out[i, c] = max over the edges e of query i of w[e, c] * x[col[e], c];
+ *   arg (Nq, C) int64 = the winning edge (absolute index, the first maximum); a query without an edge gives 0.0 and
+ *   -1: the comparison rule of tp3d_segment_max_fwd_f32, and bit-equal to it on the rows w * x[col].  A col outside
+ *   [0, M) counts as a zero feature row.
+ *   bwd: d_w (E, ldw) OVERWRITTEN: dout[i, c] * x[col[e], c] at the winning edge, zero elsewhere, padding columns
+ *   zero.  g_x (E, ldw) or NULL, OVERWRITTEN alike with dout[i, c] * w[e, c]: the sparse edge rows whose sum per
+ *   support row is the gradient wrt x -- tp3d_rows_scatter_bwd_f32 with B = 1, L = E, div = 1, idx = col, ld = ldw,
+ *   col0 = 0.  Atomic-free, bitwise reproducible. */
+int tp3d_rsconv_msgmax_fwd_f32(const float *w, int ldw, const float *x, int ldx, const int64_t *col,
+                               const int64_t *edge_start, int64_t Nq, int64_t M, int64_t E, int C, float *out,
+                               int64_t *arg, void *stream);
+int tp3d_rsconv_msgmax_bwd_f32(const float *dout, const int64_t *arg, const float *w, int ldw, const float *x, int ldx,
+                               const int64_t *col, const int64_t *edge_start, int64_t Nq, int64_t M, int64_t E, int C,
+                               float *d_w, float *g_x, void *stream);
+
+/* =====================================================================================================
  * Launch plans (host arithmetic only, no device work): what an entry point WILL do for given sizes -- how it
  * splits the rows, how many partial rows it writes, how it carves its workspace.  tests/test_plans_cpu.py sweeps
  * them against the workspace-size queries above, so that "the extent a kernel writes <= the size the caller was

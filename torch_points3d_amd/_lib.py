@@ -79,6 +79,9 @@ SIGNATURES = {
     "tp3d_pointconv_rows_f32": [_p, _p, _p, _p, _p, _l, _l, _l, _i, _i, _p, _p],
     "tp3d_segment_max_fwd_f32": [_p, _p, _l, _l, _i, _i, _p, _p, _p],
     "tp3d_segment_max_bwd_f32": [_p, _p, _p, _l, _l, _i, _i, _p, _p],
+    "tp3d_rsconv_relation_rows_f32": [_p, _p, _p, _p, _l, _l, _l, _i, _p, _p],
+    "tp3d_rsconv_msgmax_fwd_f32": [_p, _i, _p, _i, _p, _p, _l, _l, _l, _i, _p, _p, _p],
+    "tp3d_rsconv_msgmax_bwd_f32": [_p, _p, _p, _i, _p, _i, _p, _p, _l, _l, _l, _i, _p, _p, _p],
     # launch plans (host arithmetic; the last argument is a HOST int64 array)
     "tp3d_gemm_tn_plan": [_l, _i, _i, _p],
     "tp3d_gemm_tn_x3_plan": [_l, _i, _i, _p],

@@ -18,7 +18,8 @@ import torch
 from . import _lib
 
 __all__ = ["furthest_point_sample", "ball_query", "three_nn", "three_interpolate", "grouping_operation"]
-# (message-passing side: fps_quota, fps_ragged, radius_edges, pointconv_rows, segment_max -- further down)
+# (message-passing side: fps_quota, fps_ragged, radius_edges, pointconv_rows, segment_max, rsconv_relation_rows,
+# rsconv_msgmax -- further down)
 
 
 def _dev(*tensors):
@@ -251,6 +252,100 @@ def segment_max(rows, seg, C=None, return_argmax=False):
     if C > rows.shape[1]:
         raise ValueError("C exceeds the row length")
     out, arg = _SegmentMax.apply(rows, _i64(seg), C)
+    return (out, arg) if return_argmax else out
+
+
+def _check_csr(edge_start, col, nq):
+    if edge_start.dim() != 1 or col.dim() != 1 or edge_start.numel() != nq + 1:
+        raise ValueError("edge_start must have one entry per query plus one, col one per edge")
+
+
+def rsconv_relation_rows(pos_s, pos_q, edge_start, col, ld=None):
+    """The relation rows of RSConv, [|d|, d = pos_q[i] - pos_s[j], pos_q[i], pos_s[j]] per edge (j -> i): pos_s (M,3),
+    pos_q (Nq,3), CSR edges -> (E, ld) float32, ld >= 10 (default 12: a multiple of 4, zero padded).  No gradient."""
+    dev = _dev(pos_s, pos_q, edge_start, col)
+    ld = 12 if ld is None else int(ld)
+    if ld < 10:
+        raise ValueError("ld must be at least 10")
+    if pos_s.dim() != 2 or pos_s.shape[1] != 3 or pos_q.dim() != 2 or pos_q.shape[1] != 3:
+        raise ValueError("pos_s and pos_q must be (M, 3) and (Nq, 3)")
+    _check_csr(edge_start, col, pos_q.shape[0])
+    pos_s, pos_q, edge_start, col = _f32(pos_s), _f32(pos_q), _i64(edge_start), _i64(col)
+    M, Nq, E = pos_s.shape[0], pos_q.shape[0], col.shape[0]
+    out = torch.empty((E, ld), dtype=torch.float32, device=dev)
+    if E and Nq:
+        with _lib.on_device(dev):
+            _lib.call("tp3d_rsconv_relation_rows_f32", _lib.ptr(pos_s), _lib.ptr(pos_q), _lib.ptr(edge_start),
+                      _lib.ptr(col), Nq, M, E, ld, _lib.ptr(out), _lib.stream_ptr(dev))
+    return out
+
+
+class _RSConvMsgMax(torch.autograd.Function):
+    """out (Nq, C) = max over the edges of a query of w[e] * x[col[e]];  differentiable wrt w and x."""
+
+    @staticmethod
+    def forward(ctx, w, x, edge_start, col, C):
+        dev = w.device
+        wf, xf = w.detach().float().contiguous(), x.detach().float().contiguous()
+        E, ldw = wf.shape
+        M, ldx = xf.shape
+        Nq = edge_start.numel() - 1
+        out = torch.empty((Nq, C), dtype=torch.float32, device=dev)
+        arg = torch.empty((Nq, C), dtype=torch.int64, device=dev)
+        if E == 0:  # nothing to read: every query is without an edge
+            out.zero_()
+            arg.fill_(-1)
+        elif Nq and C:
+            with _lib.on_device(dev):
+                _lib.call("tp3d_rsconv_msgmax_fwd_f32", _lib.ptr(wf), ldw, _lib.ptr(xf), ldx, _lib.ptr(col),
+                          _lib.ptr(edge_start), Nq, M, E, C, _lib.ptr(out), _lib.ptr(arg), _lib.stream_ptr(dev))
+        ctx.save_for_backward(wf, xf, edge_start, col, arg)
+        ctx.C = C
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, g, _garg):
+        wf, xf, edge_start, col, arg = ctx.saved_tensors
+        C = ctx.C
+        E, ldw = wf.shape
+        M, ldx = xf.shape
+        Nq = edge_start.numel() - 1
+        dev = wf.device
+        want_x = ctx.needs_input_grad[1]
+        d_w = torch.empty((E, ldw), dtype=torch.float32, device=dev)
+        dx = torch.zeros((M, ldx), dtype=torch.float32, device=dev) if want_x else None
+        if E and Nq and ldw:
+            g = g.float().contiguous()
+            g_x = torch.empty((E, ldw), dtype=torch.float32, device=dev) if want_x and C else None
+            with _lib.on_device(dev):
+                _lib.call("tp3d_rsconv_msgmax_bwd_f32", _lib.ptr(g), _lib.ptr(arg), _lib.ptr(wf), ldw, _lib.ptr(xf), ldx,
+                          _lib.ptr(col), _lib.ptr(edge_start), Nq, M, E, C, _lib.ptr(d_w), _lib.ptr(g_x),
+                          _lib.stream_ptr(dev))
+                if g_x is not None:
+                    dxc = dx if ldx == C else torch.empty((M, C), dtype=torch.float32, device=dev)
+                    ws, nbytes = _lib.scatter_workspace(1, E, M, False, dev)
+                    _lib.call("tp3d_rows_scatter_bwd_f32", _lib.ptr(g_x), _lib.ptr(col), None, 1, E, 1, M, ldw, 0, C,
+                              _lib.ptr(dxc), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+                    if dxc is not dx:
+                        dx[:, :C] = dxc
+        return (d_w if ctx.needs_input_grad[0] else None), dx, None, None, None
+
+
+def rsconv_msgmax(w, x, edge_start, col, C=None, return_argmax=False):
+    """The aggregation of RSConv, fused: out (Nq, C) = max over the edges e of query i of w[e, c] * x[col[e], c], with
+    w (E, ldw) the per-edge weights, x (M, ldx) the support features and C <= min(ldw, ldx) (default: ldx; columns
+    past C are ignored).  Indistinguishable from segment_max(w[:, :C] * x[col, :C], edge_start): the first maximum
+    wins, a query without an edge gives 0.0 (argmax -1, else the absolute edge index).  Differentiable wrt w and x."""
+    dev = _dev(w, x, edge_start, col)
+    if w.dim() != 2 or x.dim() != 2:
+        raise ValueError("w must be (E, ldw) and x (M, ldx)")
+    C = x.shape[1] if C is None else int(C)
+    if C < 0 or C > w.shape[1] or C > x.shape[1]:
+        raise ValueError("C exceeds the row length of w or x")
+    if edge_start.dim() != 1 or edge_start.numel() < 1 or col.dim() != 1 or col.numel() != w.shape[0]:
+        raise ValueError("edge_start must be (Nq + 1,) and col must have one entry per row of w")
+    out, arg = _RSConvMsgMax.apply(w, x, _i64(edge_start), _i64(col), C)
     return (out, arg) if return_argmax else out
 
 
