@@ -208,9 +208,12 @@ class _Block(nn.Module):
         self.up = up
 
 
-class PointNet2MP(nn.Module):
-    """the nested network: SAModule x n, GlobalBaseModule, FPModule x (n + 1), relu(lin1) -> lin2 -> lin3 -> log_softmax
-    (no dropout).  forward returns every stage: sa1 .. sa<n>, glob, fp0 .. fp<n>, out."""
+class NestedMP(nn.Module):
+    """the nested network: down module x n, GlobalBaseModule, FPModule x (n + 1), relu(lin1) -> lin2 -> lin3 ->
+    log_softmax (no dropout).  forward returns every stage: <STAGE>1 .. <STAGE>n, glob, fp0 .. fp<n>, out.  A subclass
+    names STAGE, builds the down module from the state_dict (`down_of(sd, prefix)`) and picks a level's edges from the
+    plan (`edges_of(plan, i)`)."""
+    STAGE = None
 
     def __init__(self, sd):
         super().__init__()
@@ -222,8 +225,7 @@ class PointNet2MP(nn.Module):
         block = _Block(FPModule(_mlp_of(sd, deep + "up.nn.")), inner=GlobalBaseModule(_mlp_of(sd, deep + "inner.nn.")))
         for i in range(n - 1, -1, -1):
             at = "model." + "submodule." * i
-            block = _Block(FPModule(_mlp_of(sd, at + "up.nn.")), down=SAModule(_mlp_of(sd, at + "down._conv.local_nn.")),
-                           submodule=block)
+            block = _Block(FPModule(_mlp_of(sd, at + "up.nn.")), down=self.down_of(sd, at + "down."), submodule=block)
         self.model = block
         for name in ("lin1", "lin2", "lin3"):
             w = sd[name + ".weight"]
@@ -247,15 +249,15 @@ class PointNet2MP(nn.Module):
 
     def forward(self, x, pos, batch, plan):
         """plan (see `search_plan`): idx[i], edges[i] (one (edge_start, col) per scale) of level i, knn[j] the table of
-        feature-propagation module j (fp0 is the innermost one)"""
+        feature-propagation module j (fp0 is the innermost one); x may be None where the down module takes that"""
         blocks, n = self.blocks(), self.levels
         rec = {}
         lv = [(x, pos, batch)]
         for i in range(n):
             x_i, pos_i, batch_i = lv[-1]
             idx = plan["idx"][i]
-            lv.append((blocks[i].down(x_i, pos_i, idx, plan["edges"][i]), pos_i[idx], batch_i[idx]))
-            rec["sa%d" % (i + 1)] = lv[-1][0]
+            lv.append((blocks[i].down(x_i, pos_i, idx, self.edges_of(plan, i)), pos_i[idx], batch_i[idx]))
+            rec["%s%d" % (self.STAGE, i + 1)] = lv[-1][0]
         x_n, pos_n, batch_n = lv[-1]
         cur = rec["glob"] = blocks[n].inner(x_n, pos_n, batch_n)
         cur_pos = pos_n.new_zeros(cur.shape[0], 3)
@@ -265,6 +267,19 @@ class PointNet2MP(nn.Module):
             cur_pos = pos_s
         rec["out"] = F.log_softmax(self.lin3(self.lin2(F.relu(self.lin1(cur)))), dim=-1)
         return rec
+
+
+class PointNet2MP(NestedMP):
+    """NestedMP over SAModule: stages sa1 .. sa<n>, every scale's edges of a level"""
+    STAGE = "sa"
+
+    @staticmethod
+    def down_of(sd, prefix):
+        return SAModule(_mlp_of(sd, prefix + "_conv.local_nn."))
+
+    @staticmethod
+    def edges_of(plan, i):
+        return plan["edges"][i]
 
 
 def search_plan(oracle, pos, batch, ratios, radius, caps, up_k):

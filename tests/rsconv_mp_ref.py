@@ -84,56 +84,14 @@ class RSConvDown(nn.Module):
         return self._conv(x, (pos, pos[idx]), edges)
 
 
-class RSConvMP(nn.Module):
-    """the nested network: RSConvDown x n, GlobalBaseModule, FPModule x (n + 1), relu(lin1) -> lin2 -> lin3 ->
-    log_softmax (no dropout).  forward returns every stage: rs1 .. rs<n>, glob, fp0 .. fp<n>, out."""
+class RSConvMP(mp.NestedMP):
+    """pointnet2_mp_ref.NestedMP over RSConvDown: stages rs1 .. rs<n>, the one scale's edges of a level"""
+    STAGE = "rs"
 
-    def __init__(self, sd):
-        super().__init__()
-        n = 0
-        while ("model." + "submodule." * n + "down._conv.local_nn.0.0.weight") in sd:
-            n += 1
-        self.levels = n
-        deep = "model." + "submodule." * n
-        block = mp._Block(mp.FPModule(mp._mlp_of(sd, deep + "up.nn.")),
-                          inner=mp.GlobalBaseModule(mp._mlp_of(sd, deep + "inner.nn.")))
-        for i in range(n - 1, -1, -1):
-            at = "model." + "submodule." * i
-            down = RSConvDown(mp._mlp_of(sd, at + "down._conv.local_nn."), mp._mlp_of(sd, at + "down._conv.global_nn."))
-            block = mp._Block(mp.FPModule(mp._mlp_of(sd, at + "up.nn.")), down=down, submodule=block)
-        self.model = block
-        for name in ("lin1", "lin2", "lin3"):
-            w = sd[name + ".weight"]
-            setattr(self, name, nn.Linear(w.shape[1], w.shape[0]))
+    @staticmethod
+    def down_of(sd, prefix):
+        return RSConvDown(mp._mlp_of(sd, prefix + "_conv.local_nn."), mp._mlp_of(sd, prefix + "_conv.global_nn."))
 
-    @classmethod
-    def from_state_dict(cls, sd, dtype=torch.float64):
-        return mp._loaded(cls(sd), sd, dtype)
-
-    def blocks(self):
-        out, b = [], self.model
-        for _ in range(self.levels + 1):
-            out.append(b)
-            b = getattr(b, "submodule", None)
-        return out
-
-    def forward(self, x, pos, batch, plan):
-        """plan (pointnet2_mp_ref.search_plan): idx[i], edges[i][0] = (edge_start, col) of level i, knn[j] the table of
-        feature-propagation module j (fp0 is the innermost one); x may be None"""
-        blocks, n = self.blocks(), self.levels
-        rec = {}
-        lv = [(x, pos, batch)]
-        for i in range(n):
-            x_i, pos_i, batch_i = lv[-1]
-            idx = plan["idx"][i]
-            lv.append((blocks[i].down(x_i, pos_i, idx, plan["edges"][i][0]), pos_i[idx], batch_i[idx]))
-            rec["rs%d" % (i + 1)] = lv[-1][0]
-        x_n, pos_n, batch_n = lv[-1]
-        cur = rec["glob"] = blocks[n].inner(x_n, pos_n, batch_n)
-        cur_pos = pos_n.new_zeros(cur.shape[0], 3)
-        for j in range(n + 1):
-            x_s, pos_s, _ = lv[n - j]
-            cur = rec["fp%d" % j] = blocks[n - j].up(cur, cur_pos, x_s, pos_s, plan["knn"][j])
-            cur_pos = pos_s
-        rec["out"] = F.log_softmax(self.lin3(self.lin2(F.relu(self.lin1(cur)))), dim=-1)
-        return rec
+    @staticmethod
+    def edges_of(plan, i):
+        return plan["edges"][i][0]

@@ -6,19 +6,17 @@
 //
 // All four are streams over (edges, ld) rows: a wave owns one query / segment, its lanes walk the row-major
 // elements of that query's edges, so every store (and the feature loads of one support row) is contiguous.
-#include "tp3d_common.h"
+// The launch shape, the run bounds and the element walk are edge_run.h's.
+#include "edge_run.h"
 
 namespace tp3d {
 
-constexpr int PC_BLOCK = 256;                // 4 waves, one query / segment piece each
-constexpr int PC_WAVES = PC_BLOCK / kWave;
-
 // ---- table -> edges ---------------------------------------------------------------------------------------------
 // counts[i + 1] = number of slots >= 0 in row i of the -1 padded table (one wave per row, 64 slots per step)
-__global__ __launch_bounds__(PC_BLOCK) void table_count_kernel(const int64_t *__restrict__ table, int64_t Nq, int W,
+__global__ __launch_bounds__(ER_BLOCK) void table_count_kernel(const int64_t *__restrict__ table, int64_t Nq, int W,
                                                                 int64_t *__restrict__ edge_start)
 {
-    const int64_t i = (int64_t)blockIdx.x * PC_WAVES + threadIdx.x / kWave;
+    const int64_t i = (int64_t)blockIdx.x * ER_WAVES + threadIdx.x / kWave;
     if (i >= Nq) return;
     const int lane = lane_id();
     int n = 0;
@@ -74,11 +72,11 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_kernel(int64_t *__restrict__ 
 }
 
 // col[edge_start[i] + rank] = table[i, s] for the slots >= 0 of row i, in slot order
-__global__ __launch_bounds__(PC_BLOCK) void table_fill_kernel(const int64_t *__restrict__ table, int64_t Nq, int W,
+__global__ __launch_bounds__(ER_BLOCK) void table_fill_kernel(const int64_t *__restrict__ table, int64_t Nq, int W,
                                                                const int64_t *__restrict__ edge_start, int64_t E,
                                                                int64_t *__restrict__ col)
 {
-    const int64_t i = (int64_t)blockIdx.x * PC_WAVES + threadIdx.x / kWave;
+    const int64_t i = (int64_t)blockIdx.x * ER_WAVES + threadIdx.x / kWave;
     if (i >= Nq) return;
     const int lane = lane_id();
     int64_t at = edge_start[i];
@@ -93,8 +91,8 @@ __global__ __launch_bounds__(PC_BLOCK) void table_fill_kernel(const int64_t *__r
 }
 
 // ---- edge rows --------------------------------------------------------------------------------------------------
-// out[e, :] = [ x[col[e], 0:C] | pos_s[col[e]] - pos_q[i] | 0 .. ] for the edges e of query i
-__global__ __launch_bounds__(PC_BLOCK) void pointconv_rows_kernel(const float *__restrict__ x,
+// out[e, :] = [ x[col[e], 0:C] | pos_s[col[e]] - pos_q[i] | 0 .. ] for the edges e of query i (one piece per query)
+__global__ __launch_bounds__(ER_BLOCK) void pointconv_rows_kernel(const float *__restrict__ x,
                                                                    const float *__restrict__ pos_s,
                                                                    const float *__restrict__ pos_q,
                                                                    const int64_t *__restrict__ edge_start,
@@ -102,45 +100,37 @@ __global__ __launch_bounds__(PC_BLOCK) void pointconv_rows_kernel(const float *_
                                                                    int64_t M, int64_t E, int C, int ld,
                                                                    float *__restrict__ out)
 {
-    const int64_t i = (int64_t)blockIdx.x * PC_WAVES + threadIdx.x / kWave;
-    if (i >= Nq) return;
-    const int lane = lane_id();
-    const int64_t e0 = edge_start[i];
-    int64_t e1 = edge_start[i + 1];
-    if (e1 > E) e1 = E;
-    if (e0 < 0 || e0 >= e1) return;
+    int64_t i, e0, e1;
+    int one;
+    if (!wave_item(Nq, 1, i, one)) return;
+    run_bounds(edge_start, i, E, e0, e1);
+    if (e0 >= e1) return;
     const float qx = pos_q[i * 3 + 0], qy = pos_q[i * 3 + 1], qz = pos_q[i * 3 + 2];
-    const int64_t n = (e1 - e0) * ld;
-    float *o = out + e0 * ld;
-    for (int64_t f = lane; f < n; f += kWave) {
-        const int64_t r = f / ld;
-        const int c = (int)(f - r * ld);
-        const int64_t j = col[e0 + r];
+    walk_rows(e0, e1, ld, [&](int64_t e, int c, int64_t at) {
+        const int64_t j = col[e];
         float v = 0.0f;
         if (j >= 0 && j < M) {
             if (c < C) v = x[j * C + c];
-            else if (c < C + 3) v = pos_s[j * 3 + (c - C)] - (c == C ? qx : (c == C + 1 ? qy : qz));
+            else if (c < C + 3) v = pos_s[j * 3 + (c - C)] - pick3(c - C, qx, qy, qz);
         }
-        o[f] = v;
-    }
+        out[at] = v;
+    });
 }
 
 // ---- segmented max ----------------------------------------------------------------------------------------------
 // one wave per (segment, 64 channels): rows in ascending order, strict '>' keeps the first maximum
-__global__ __launch_bounds__(PC_BLOCK) void segment_max_fwd_kernel(const float *__restrict__ rows,
+__global__ __launch_bounds__(ER_BLOCK) void segment_max_fwd_kernel(const float *__restrict__ rows,
                                                                     const int64_t *__restrict__ seg, int64_t S,
                                                                     int64_t E, int C, int ld, int chunks,
                                                                     float *__restrict__ out,
                                                                     int64_t *__restrict__ argmax)
 {
-    const int64_t w = (int64_t)blockIdx.x * PC_WAVES + threadIdx.x / kWave;
-    if (w >= S * chunks) return;
-    const int64_t s = w / chunks;
-    const int c = (int)(w - s * chunks) * kWave + lane_id();
+    int64_t s, r0, r1;
+    int chunk;
+    if (!wave_item(S, chunks, s, chunk)) return;
+    const int c = chunk * kWave + lane_id();
     if (c >= C) return;
-    int64_t r0 = seg[s], r1 = seg[s + 1];
-    if (r0 < 0) r0 = 0;
-    if (r1 > E) r1 = E;
+    run_bounds(seg, s, E, r0, r1);
     float best = 0.0f;
     int64_t arg = -1;
     if (r0 < r1) {
@@ -160,37 +150,22 @@ __global__ __launch_bounds__(PC_BLOCK) void segment_max_fwd_kernel(const float *
 
 // d_rows[r, c] = dout[s, c] where r is the winning row of (s, c), else 0 (padding columns 0): every row belongs to
 // one segment, so the rows are written, not accumulated.  A segment is cut into `parts` pieces of rows, a wave each.
-__global__ __launch_bounds__(PC_BLOCK) void segment_max_bwd_kernel(const float *__restrict__ dout,
+__global__ __launch_bounds__(ER_BLOCK) void segment_max_bwd_kernel(const float *__restrict__ dout,
                                                                     const int64_t *__restrict__ argmax,
                                                                     const int64_t *__restrict__ seg, int64_t S,
                                                                     int64_t E, int C, int ld, int parts,
                                                                     float *__restrict__ d_rows)
 {
-    const int64_t w = (int64_t)blockIdx.x * PC_WAVES + threadIdx.x / kWave;
-    if (w >= S * parts) return;
-    const int64_t s = w / parts;
-    const int part = (int)(w - s * parts);
-    int64_t r0 = seg[s], r1 = seg[s + 1];
-    if (r0 < 0) r0 = 0;
-    if (r1 > E) r1 = E;
-    if (r0 >= r1) return;
-    const int64_t per = (r1 - r0 + parts - 1) / parts;
-    const int64_t a = r0 + part * per;
-    const int64_t b = a + per < r1 ? a + per : r1;
-    if (a >= b) return;
-    const int64_t n = (b - a) * ld;
-    float *o = d_rows + a * ld;
-    for (int64_t f = lane_id(); f < n; f += kWave) {
-        const int64_t r = f / ld;
-        const int c = (int)(f - r * ld);
+    int64_t s, a, b;
+    int part;
+    if (!wave_item(S, parts, s, part)) return;
+    run_piece(seg, s, E, part, parts, a, b);
+    walk_rows(a, b, ld, [&](int64_t r, int c, int64_t at) {
         float v = 0.0f;
-        if (c < C && argmax[s * C + c] == a + r) v = dout[s * C + c];
-        o[f] = v;
-    }
+        if (c < C && argmax[s * C + c] == r) v = dout[s * C + c];
+        d_rows[at] = v;
+    });
 }
-
-static inline bool grid_ok(int64_t waves) { return (waves + PC_WAVES - 1) / PC_WAVES <= INT32_MAX; }
-static inline dim3 grid_of(int64_t waves) { return dim3((unsigned)((waves + PC_WAVES - 1) / PC_WAVES)); }
 
 }  // namespace tp3d
 
@@ -203,7 +178,7 @@ TP3D_EXPORT int tp3d_table_edge_start_i64(const int64_t *table, int64_t Nq, int 
     if (Nq == 0) return zero_async(edge_start, sizeof(int64_t), s);
     if (!table && max_num > 0) return TP3D_E_BADARG;
     if (!grid_ok(Nq)) return TP3D_E_TOOBIG;
-    hipLaunchKernelGGL(table_count_kernel, grid_of(Nq), dim3(PC_BLOCK), 0, s, table, Nq, max_num, edge_start);
+    hipLaunchKernelGGL(table_count_kernel, grid_of(Nq), dim3(ER_BLOCK), 0, s, table, Nq, max_num, edge_start);
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, edge_start, Nq);
     return check_launch();
 }
@@ -216,7 +191,7 @@ TP3D_EXPORT int tp3d_table_edge_col_i64(const int64_t *table, const int64_t *edg
     if (Nq == 0 || E == 0 || max_num == 0) return TP3D_OK;
     if (!table || !edge_start || !col) return TP3D_E_BADARG;
     if (!grid_ok(Nq)) return TP3D_E_TOOBIG;
-    hipLaunchKernelGGL(table_fill_kernel, grid_of(Nq), dim3(PC_BLOCK), 0, (hipStream_t)stream, table, Nq, max_num,
+    hipLaunchKernelGGL(table_fill_kernel, grid_of(Nq), dim3(ER_BLOCK), 0, (hipStream_t)stream, table, Nq, max_num,
                        edge_start, E, col);
     return check_launch();
 }
@@ -230,7 +205,7 @@ TP3D_EXPORT int tp3d_pointconv_rows_f32(const float *x, const float *pos_s, cons
     if (Nq == 0 || E == 0) return TP3D_OK;
     if (!pos_s || !pos_q || !edge_start || !col || !out || (C > 0 && !x)) return TP3D_E_BADARG;
     if (!grid_ok(Nq)) return TP3D_E_TOOBIG;
-    hipLaunchKernelGGL(pointconv_rows_kernel, grid_of(Nq), dim3(PC_BLOCK), 0, (hipStream_t)stream, x, pos_s, pos_q,
+    hipLaunchKernelGGL(pointconv_rows_kernel, grid_of(Nq), dim3(ER_BLOCK), 0, (hipStream_t)stream, x, pos_s, pos_q,
                        edge_start, col, Nq, M, E, C, ld, out);
     return check_launch();
 }
@@ -244,7 +219,7 @@ TP3D_EXPORT int tp3d_segment_max_fwd_f32(const float *rows, const int64_t *seg, 
     if (!seg || !out || !argmax || (E > 0 && !rows)) return TP3D_E_BADARG;
     const int chunks = (C + kWave - 1) / kWave;
     if (!grid_ok(S * chunks)) return TP3D_E_TOOBIG;
-    hipLaunchKernelGGL(segment_max_fwd_kernel, grid_of(S * chunks), dim3(PC_BLOCK), 0, (hipStream_t)stream, rows, seg,
+    hipLaunchKernelGGL(segment_max_fwd_kernel, grid_of(S * chunks), dim3(ER_BLOCK), 0, (hipStream_t)stream, rows, seg,
                        S, E, C, ld, chunks, out, argmax);
     return check_launch();
 }
@@ -256,11 +231,9 @@ TP3D_EXPORT int tp3d_segment_max_bwd_f32(const float *dout, const int64_t *argma
     if (S < 0 || E < 0 || C < 0 || ld < C) return TP3D_E_BADARG;
     if (S == 0 || E == 0 || ld == 0) return TP3D_OK;
     if (!dout || !argmax || !seg || !d_rows) return TP3D_E_BADARG;
-    // rows per wave: about 64 (the per-query segments of PointConv: one piece; a cloud of the global pool: many)
-    int64_t parts = (E / S + 63) / 64;
-    parts = parts < 1 ? 1 : (parts > 1024 ? 1024 : parts);
+    const int64_t parts = run_parts(S, E);
     if (!grid_ok(S * parts)) return TP3D_E_TOOBIG;
-    hipLaunchKernelGGL(segment_max_bwd_kernel, grid_of(S * parts), dim3(PC_BLOCK), 0, (hipStream_t)stream, dout,
+    hipLaunchKernelGGL(segment_max_bwd_kernel, grid_of(S * parts), dim3(ER_BLOCK), 0, (hipStream_t)stream, dout,
                        argmax, seg, S, E, C, ld, (int)parts, d_rows);
     return check_launch();
 }

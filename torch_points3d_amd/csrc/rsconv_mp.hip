@@ -6,10 +6,10 @@
 // local_nn has BatchNorm over ALL edges, so M (E, C) has to exist in memory; the gathered features x[col], the
 // product and the rows the max reads do not: msgmax reads w and x and writes (Nq, C) only.
 //
-// Launch shapes (blocks of 256 = 4 waves, a wave owns one query, as csrc/pointconv.hip):
-//   * relation rows / msgmax backward: the lanes walk the row-major elements of the query's edge run, (run, ld)
-//     floats, so every store is contiguous.  A run longer than 64 edges is cut into `parts` pieces of a wave each
-//     (the finder's cap is 64: one piece; the entry points take any CSR).
+// Launch shapes (edge_run.h: blocks of 256 = 4 waves, a wave owns one query or one piece of its run):
+//   * relation rows / msgmax backward: walk_rows over the (run, ld) floats of the query's edge run, so every store
+//     is contiguous.  A run longer than 64 edges is cut into `parts` pieces of a wave each (the finder's cap is 64:
+//     one piece; the entry points take any CSR).
 //   * msgmax forward: one wave per (query, chunk of 64 channels).  A chunk of cw <= 64 channels puts G = 64 / cw
 //     edges side by side in the wave (lane = edge_in_step * cw + channel): C = 3 walks 21 edges per step instead of
 //     one, C >= 33 one edge per step with the lane as the channel, loads of one edge row contiguous.  Four steps are
@@ -27,64 +27,40 @@
 // row and reading arg / d_out / w through it, which keeps the edge rows out of memory -- needs the same inversion
 // and turns the contiguous row reads into one (query, channel) probe of `arg` per (edge, channel); it was not built.
 // No floating-point atomics anywhere.
-#include "tp3d_common.h"
+#include "edge_run.h"
 
 namespace tp3d {
 
-constexpr int RS_BLOCK = 256;
-constexpr int RS_WAVES = RS_BLOCK / kWave;
 constexpr int RS_LD_MIN = 10;
 
-static inline bool rs_grid_ok(int64_t waves) { return (waves + RS_WAVES - 1) / RS_WAVES <= INT32_MAX; }
-static inline dim3 rs_grid_of(int64_t waves) { return dim3((unsigned)((waves + RS_WAVES - 1) / RS_WAVES)); }
-
-// the piece [a, b) of the run of query s that wave `part` of `parts` owns (empty: a >= b)
-__device__ __forceinline__ void run_piece(const int64_t *__restrict__ edge_start, int64_t s, int64_t E, int part,
-                                          int parts, int64_t &a, int64_t &b)
-{
-    int64_t r0 = edge_start[s], r1 = edge_start[s + 1];
-    if (r0 < 0) r0 = 0;
-    if (r1 > E) r1 = E;
-    a = b = 0;
-    if (r0 >= r1) return;
-    const int64_t per = (r1 - r0 + parts - 1) / parts;
-    a = r0 + part * per;
-    b = a + per < r1 ? a + per : r1;
-}
-
 // out[e, :] = [ |d|, d = pos_q[i] - pos_s[col[e]], pos_q[i], pos_s[col[e]], 0 .. ] for the edges e of query i
-__global__ __launch_bounds__(RS_BLOCK) void rsconv_relation_rows_kernel(const float *__restrict__ pos_s,
+__global__ __launch_bounds__(ER_BLOCK) void rsconv_relation_rows_kernel(const float *__restrict__ pos_s,
                                                                          const float *__restrict__ pos_q,
                                                                          const int64_t *__restrict__ edge_start,
                                                                          const int64_t *__restrict__ col, int64_t Nq,
                                                                          int64_t M, int64_t E, int ld, int parts,
                                                                          float *__restrict__ out)
 {
-    const int64_t w = (int64_t)blockIdx.x * RS_WAVES + threadIdx.x / kWave;
-    if (w >= Nq * parts) return;
-    const int64_t i = w / parts;
-    int64_t a, b;
-    run_piece(edge_start, i, E, (int)(w - i * parts), parts, a, b);
+    int64_t i, a, b;
+    int part;
+    if (!wave_item(Nq, parts, i, part)) return;
+    run_piece(edge_start, i, E, part, parts, a, b);
     if (a >= b) return;
     const float q[3] = {pos_q[i * 3 + 0], pos_q[i * 3 + 1], pos_q[i * 3 + 2]};
-    const int64_t n = (b - a) * ld;
-    float *o = out + a * ld;
-    for (int64_t f = lane_id(); f < n; f += kWave) {
-        const int64_t r = f / ld;
-        const int c = (int)(f - r * ld);
-        const int64_t j = col[a + r];
+    walk_rows(a, b, ld, [&](int64_t e, int c, int64_t at) {
+        const int64_t j = col[e];
         float v = 0.0f;
         if (j >= 0 && j < M && c < RS_LD_MIN) {
             if (c == 0) {
                 v = sqrtf(sqdist3(q[0], q[1], q[2], pos_s[j * 3 + 0], pos_s[j * 3 + 1], pos_s[j * 3 + 2]));
             } else {
                 const int k = (c - 1) % 3;
-                const float qv = k == 0 ? q[0] : (k == 1 ? q[1] : q[2]);
+                const float qv = pick3(k, q[0], q[1], q[2]);
                 v = c <= 3 ? qv - pos_s[j * 3 + k] : (c <= 6 ? qv : pos_s[j * 3 + k]);
             }
         }
-        o[f] = v;
-    }
+        out[at] = v;
+    });
 }
 
 // one product of edge e, channel c (a col outside [0, M) counts as a zero feature row)
@@ -95,26 +71,24 @@ __device__ __forceinline__ float msg_of(const float *__restrict__ w, int ldw, co
     return w[e * ldw + c] * xv;
 }
 
-__global__ __launch_bounds__(RS_BLOCK) void rsconv_msgmax_fwd_kernel(const float *__restrict__ w, int ldw,
+__global__ __launch_bounds__(ER_BLOCK) void rsconv_msgmax_fwd_kernel(const float *__restrict__ w, int ldw,
                                                                       const float *__restrict__ x, int ldx,
                                                                       const int64_t *__restrict__ col,
                                                                       const int64_t *__restrict__ edge_start,
                                                                       int64_t Nq, int64_t M, int64_t E, int C, int chunks,
                                                                       float *__restrict__ out, int64_t *__restrict__ arg)
 {
-    const int64_t wv = (int64_t)blockIdx.x * RS_WAVES + threadIdx.x / kWave;
-    if (wv >= Nq * chunks) return;  // wave-uniform: the shuffles below see whole waves
-    const int64_t i = wv / chunks;
-    const int c0 = (int)(wv - i * chunks) * kWave;
+    int64_t i, e0, e1;
+    int chunk;
+    if (!wave_item(Nq, chunks, i, chunk)) return;  // wave-uniform: the shuffles below see whole waves
+    const int c0 = chunk * kWave;
     const int cw = C - c0 < kWave ? C - c0 : kWave;  // channels of this chunk, >= 1
     const int G = kWave / cw;                        // edges side by side
     const int lane = lane_id();
     const int g = lane / cw;
     const int c = c0 + (lane - g * cw);
     const bool live = g < G;
-    int64_t e0 = edge_start[i], e1 = edge_start[i + 1];
-    if (e0 < 0) e0 = 0;
-    if (e1 > E) e1 = E;
+    run_bounds(edge_start, i, E, e0, e1);
     float best = 0.0f;
     int64_t at = -1;
     if (live) {
@@ -162,7 +136,7 @@ __global__ __launch_bounds__(RS_BLOCK) void rsconv_msgmax_fwd_kernel(const float
 
 // d_w[e, c] = d_out[i, c] * x[col[e], c] and g_x[e, c] = d_out[i, c] * w[e, c] where e == arg[i, c], else 0 (padding
 // columns 0); both (E, ldw), every element written once by the wave that owns the piece of the run.  g_x may be null.
-__global__ __launch_bounds__(RS_BLOCK) void rsconv_msgmax_bwd_kernel(const float *__restrict__ dout,
+__global__ __launch_bounds__(ER_BLOCK) void rsconv_msgmax_bwd_kernel(const float *__restrict__ dout,
                                                                       const int64_t *__restrict__ arg,
                                                                       const float *__restrict__ w, int ldw,
                                                                       const float *__restrict__ x, int ldx,
@@ -171,17 +145,11 @@ __global__ __launch_bounds__(RS_BLOCK) void rsconv_msgmax_bwd_kernel(const float
                                                                       int64_t Nq, int64_t M, int64_t E, int C, int parts,
                                                                       float *__restrict__ d_w, float *__restrict__ g_x)
 {
-    const int64_t wv = (int64_t)blockIdx.x * RS_WAVES + threadIdx.x / kWave;
-    if (wv >= Nq * parts) return;
-    const int64_t i = wv / parts;
-    int64_t a, b;
-    run_piece(edge_start, i, E, (int)(wv - i * parts), parts, a, b);
-    if (a >= b) return;
-    const int64_t n = (b - a) * ldw;
-    for (int64_t f = lane_id(); f < n; f += kWave) {
-        const int64_t r = f / ldw;
-        const int c = (int)(f - r * ldw);
-        const int64_t e = a + r;
+    int64_t i, a, b;
+    int part;
+    if (!wave_item(Nq, parts, i, part)) return;
+    run_piece(edge_start, i, E, part, parts, a, b);
+    walk_rows(a, b, ldw, [&](int64_t e, int c, int64_t at) {
         float dw = 0.0f, gx = 0.0f;
         if (c < C && arg[i * C + c] == e) {
             const float g = dout[i * C + c];
@@ -189,16 +157,9 @@ __global__ __launch_bounds__(RS_BLOCK) void rsconv_msgmax_bwd_kernel(const float
             dw = g * ((j >= 0 && j < M) ? x[j * ldx + c] : 0.0f);
             gx = g * w[e * ldw + c];
         }
-        d_w[a * ldw + f] = dw;
-        if (g_x) g_x[a * ldw + f] = gx;
-    }
-}
-
-// rows per wave of the element-walking kernels: about 64 (the finder's cap: one piece per query)
-static inline int64_t rs_parts(int64_t Nq, int64_t E)
-{
-    const int64_t parts = (E / Nq + 63) / 64;
-    return parts < 1 ? 1 : (parts > 1024 ? 1024 : parts);
+        d_w[at] = dw;
+        if (g_x) g_x[at] = gx;
+    });
 }
 
 }  // namespace tp3d
@@ -211,9 +172,9 @@ TP3D_EXPORT int tp3d_rsconv_relation_rows_f32(const float *pos_s, const float *p
     if (Nq < 0 || M < 0 || E < 0 || ld < RS_LD_MIN) return TP3D_E_BADARG;
     if (Nq == 0 || E == 0) return TP3D_OK;
     if (!pos_s || !pos_q || !edge_start || !col || !out) return TP3D_E_BADARG;
-    const int64_t parts = rs_parts(Nq, E);
-    if (!rs_grid_ok(Nq * parts)) return TP3D_E_TOOBIG;
-    hipLaunchKernelGGL(rsconv_relation_rows_kernel, rs_grid_of(Nq * parts), dim3(RS_BLOCK), 0, (hipStream_t)stream, pos_s,
+    const int64_t parts = run_parts(Nq, E);
+    if (!grid_ok(Nq * parts)) return TP3D_E_TOOBIG;
+    hipLaunchKernelGGL(rsconv_relation_rows_kernel, grid_of(Nq * parts), dim3(ER_BLOCK), 0, (hipStream_t)stream, pos_s,
                        pos_q, edge_start, col, Nq, M, E, ld, (int)parts, out);
     return check_launch();
 }
@@ -227,8 +188,8 @@ TP3D_EXPORT int tp3d_rsconv_msgmax_fwd_f32(const float *w, int ldw, const float 
     if (Nq == 0 || C == 0) return TP3D_OK;
     if (!edge_start || !out || !arg || (E > 0 && (!w || !x || !col))) return TP3D_E_BADARG;
     const int chunks = (C + kWave - 1) / kWave;
-    if (!rs_grid_ok(Nq * chunks)) return TP3D_E_TOOBIG;
-    hipLaunchKernelGGL(rsconv_msgmax_fwd_kernel, rs_grid_of(Nq * chunks), dim3(RS_BLOCK), 0, (hipStream_t)stream, w, ldw, x,
+    if (!grid_ok(Nq * chunks)) return TP3D_E_TOOBIG;
+    hipLaunchKernelGGL(rsconv_msgmax_fwd_kernel, grid_of(Nq * chunks), dim3(ER_BLOCK), 0, (hipStream_t)stream, w, ldw, x,
                        ldx, col, edge_start, Nq, M, E, C, chunks, out, arg);
     return check_launch();
 }
@@ -241,9 +202,9 @@ TP3D_EXPORT int tp3d_rsconv_msgmax_bwd_f32(const float *dout, const int64_t *arg
     if (Nq < 0 || M < 0 || E < 0 || C < 0 || ldw < C || ldx < C) return TP3D_E_BADARG;
     if (Nq == 0 || E == 0 || ldw == 0) return TP3D_OK;
     if (!dout || !arg || !w || !x || !col || !edge_start || !d_w) return TP3D_E_BADARG;
-    const int64_t parts = rs_parts(Nq, E);
-    if (!rs_grid_ok(Nq * parts)) return TP3D_E_TOOBIG;
-    hipLaunchKernelGGL(rsconv_msgmax_bwd_kernel, rs_grid_of(Nq * parts), dim3(RS_BLOCK), 0, (hipStream_t)stream, dout, arg, w,
+    const int64_t parts = run_parts(Nq, E);
+    if (!grid_ok(Nq * parts)) return TP3D_E_TOOBIG;
+    hipLaunchKernelGGL(rsconv_msgmax_bwd_kernel, grid_of(Nq * parts), dim3(ER_BLOCK), 0, (hipStream_t)stream, dout, arg, w,
                        ldw, x, ldx, col, edge_start, Nq, M, E, C, (int)parts, d_w, g_x);
     return check_launch();
 }

@@ -7,8 +7,9 @@ Mirrors (same constructor arguments and attribute names -- hence state_dict keys
   * `PointConv`                        torch_geometric.nn.PointConv as modules/pointnet2/message_passing.py:20,26 uses it
   * `SAModule`                         torch_points3d/modules/pointnet2/message_passing.py:9-31 over
                                        BaseMSConvolutionDown, core/base_conv/message_passing.py:61-94
+  * `BaseConvolutionDown`              the forward of core/base_conv/message_passing.py:35-58 and 61-94, one or more scales
   * `GlobalBaseModule`, `FPModule`     torch_points3d/core/base_conv/message_passing.py:132-151, 157-176
-  * `PointNet2MP`                      conf/models/segmentation/pointnet2.yaml:5-57 (`pointnet2`, `pointnet2ms`) nested as
+  * `SegmentationMP`, `PointNet2MP`    conf/models/segmentation/pointnet2.yaml:5-57 (`pointnet2`, `pointnet2ms`) nested as
                                        models/base_architectures/unet.py:93-138 nests it, with the Segmentation_MP head
                                        (models/segmentation/base.py:27-55)
 The reference gets sampling and the radius search from torch_cluster and the max from torch_scatter; here they are
@@ -185,8 +186,34 @@ def copy_from_to(data, batch):
             setattr(batch, key, getattr(data, key, None))
 
 
-class SAModule(nn.Module):
-    """Set abstraction: sample once, then per scale search + the shared PointConv, scales concatenated."""
+class BaseConvolutionDown(nn.Module):
+    """Set abstraction: sample once, then per scale of the finder search + the shared convolution, scales concatenated.
+    A subclass sets `sampler`, `neighbour_finder` (multi-scale or not), `_conv` and `_index`."""
+
+    def conv(self, x, pos, edge_index, batch):
+        return self._conv(x, pos, edge_index)
+
+    def forward(self, data, **kwargs):
+        out = PDData()
+        x, pos, batch = data.x, data.pos, data.batch
+        idx = self.sampler(pos, batch=batch)
+        out.idx = idx
+        pos_q, batch_q = pos[idx], batch[idx]
+        finder = self.neighbour_finder
+        scales = [dict(scale_idx=s) for s in range(finder.num_scales)] if hasattr(finder, "num_scales") else [{}]
+        ms_x = []
+        for scale in scales:
+            edges = finder(pos, pos_q, batch_x=batch, batch_y=batch_q, **scale)
+            ms_x.append(self.conv(x, (pos, pos_q), edges, batch))
+        out.x = ms_x[0] if len(ms_x) == 1 else torch.cat(ms_x, -1)
+        out.pos = pos_q
+        out.batch = batch_q
+        copy_from_to(data, out)
+        return out
+
+
+class SAModule(BaseConvolutionDown):
+    """FPSSampler(ratio) + MultiscaleRadiusNeighbourFinder(radius, radius_num_point) + PointConv(MLP(down_conv_nn))."""
 
     def __init__(self, ratio=None, radius=None, radius_num_point=None, down_conv_nn=None, *args, **kwargs):
         super().__init__()
@@ -198,25 +225,6 @@ class SAModule(nn.Module):
         self._radius = radius
         self._ratio = ratio
         self._num_points = radius_num_point
-
-    def conv(self, x, pos, edge_index, batch):
-        return self._conv(x, pos, edge_index)
-
-    def forward(self, data, **kwargs):
-        out = PDData()
-        x, pos, batch = data.x, data.pos, data.batch
-        idx = self.sampler(pos, batch=batch)
-        out.idx = idx
-        pos_q, batch_q = pos[idx], batch[idx]
-        ms_x = []
-        for scale_idx in range(self.neighbour_finder.num_scales):
-            edges = self.neighbour_finder(pos, pos_q, batch_x=batch, batch_y=batch_q, scale_idx=scale_idx)
-            ms_x.append(self.conv(x, (pos, pos_q), edges, batch))
-        out.x = ms_x[0] if len(ms_x) == 1 else torch.cat(ms_x, -1)
-        out.pos = pos_q
-        out.batch = batch_q
-        copy_from_to(data, out)
-        return out
 
     def extra_repr(self):
         return "{}(ratio {}, radius {}, radius_points {})".format(self.__class__.__name__, self._ratio, self._radius,
@@ -326,33 +334,26 @@ class _UnetBlock(nn.Module):
         return self.up((self.submodule(self.down(data)), data))
 
 
-class PointNet2MP(nn.Module):
-    """PointNet2_MP segmentation network: SAModule x n, GlobalBaseModule, FPModule x (n + 1), Segmentation_MP head.
+class SegmentationMP(nn.Module):
+    """The nested network of a message-passing U-Net: down module x n, GlobalBaseModule, FPModule x (n + 1), and the
+    Segmentation_MP head.  cfg: the YAML's fields, numbers already resolved (down_conv: its down_conv_nn counts the
+    levels; up_conv: up_conv_nn, up_k, skip; innermost: aggr, nn; mlp_cls: nn, dropout); make_down(i) builds the down
+    module of level i.  forward(data) -> log-probabilities (N, num_classes); data carries pos (N,3), x and a sorted
+    batch (N)."""
 
-    cfg: a config name of mp_config ("pointnet2", "pointnet2ms") or a dict with the YAML's fields (down_conv: ratios,
-    radius, radius_num_points, down_conv_nn; up_conv: up_conv_nn, up_k, skip; innermost: aggr, nn; mlp_cls: nn, dropout),
-    numbers already resolved.  forward(data) -> log-probabilities (N, num_classes); data carries pos (N,3), x (N,input_nc),
-    and a sorted batch (N)."""
-
-    def __init__(self, cfg, input_nc, num_classes):
+    def __init__(self, cfg, num_classes, make_down):
         super().__init__()
-        if isinstance(cfg, str):
-            cfg = mp_config(cfg, input_nc)
-        down, up, inner, head = cfg["down_conv"], cfg["up_conv"], cfg["innermost"], cfg["mlp_cls"]
-        n = len(down["down_conv_nn"])
+        up, inner, head = cfg["up_conv"], cfg["innermost"], cfg["mlp_cls"]
+        n = len(cfg["down_conv"]["down_conv_nn"])
         if n + 1 != len(up["up_conv_nn"]):
             raise ValueError("up_conv_nn must list one module more than down_conv_nn (the innermost block's)")
-
-        def sa(i):
-            return SAModule(ratio=down["ratios"][i], radius=down["radius"][i], radius_num_point=down["radius_num_points"][i],
-                            down_conv_nn=down["down_conv_nn"][i], index=i)
 
         def fp(j):
             return FPModule(up_k=up["up_k"][j], up_conv_nn=up["up_conv_nn"][j], skip=up.get("skip", True), index=j)
 
         block = _UnetBlock(fp(0), inner=GlobalBaseModule(nn=inner["nn"], aggr=inner.get("aggr", "max")))
         for index in range(n - 1, -1, -1):  # the deepest level is nested first; the last one built is the input level
-            block = _UnetBlock(fp(n - index), down=sa(index), submodule=block)
+            block = _UnetBlock(fp(n - index), down=make_down(index), submodule=block)
         self.model = block
         widths = head["nn"]
         self.dropout = head.get("dropout")
@@ -369,3 +370,18 @@ class PointNet2MP(nn.Module):
         x = F.dropout(x, p=p, training=bool(self.training))
         x = self.lin3(x)
         return F.log_softmax(x, dim=-1)
+
+
+class PointNet2MP(SegmentationMP):
+    """PointNet2_MP segmentation network: SegmentationMP over SAModule.
+
+    cfg: a config name of mp_config ("pointnet2", "pointnet2ms") or a dict with the YAML's fields (down_conv: ratios,
+    radius, radius_num_points, down_conv_nn; the rest as SegmentationMP).  data.x is (N, input_nc)."""
+
+    def __init__(self, cfg, input_nc, num_classes):
+        if isinstance(cfg, str):
+            cfg = mp_config(cfg, input_nc)
+        down = cfg["down_conv"]
+        super().__init__(cfg, num_classes, lambda i: SAModule(
+            ratio=down["ratios"][i], radius=down["radius"][i], radius_num_point=down["radius_num_points"][i],
+            down_conv_nn=down["down_conv_nn"][i], index=i))

@@ -5,8 +5,8 @@ Mirrors (same constructor arguments and attribute names -- hence state_dict keys
                                   core/base_conv/message_passing.py:35-58
   * `RSConvMP`                    conf/models/segmentation/rsconv.yaml:3-55 (`RSConv_2LD`, `RSConv_4LD`, class
                                   rsconv.RSConv_MP = Segmentation_MP) nested as models/base_architectures/unet.py nests it
-The sampler, the radius search (CSR `Edges`), GlobalBaseModule, FPModule, the nested block and the head are those of
-pointnet2_mp.py.  Per edge (j -> i) the layer computes
+The sampler, the radius search (CSR `Edges`), the set-abstraction forward (BaseConvolutionDown) and the nested network
+with its head (SegmentationMP: GlobalBaseModule, FPModule) are those of pointnet2_mp.py.  Per edge (j -> i) the layer computes
 
     h_ij = [ |p_i - p_j|, p_i - p_j, p_i, p_j ]        torchpoints.rsconv_relation_rows   (E, 12), 10 used
     M_ij = local_nn(h_ij)                              fused.rows_mlp: BatchNorm over ALL edges, so M exists in memory
@@ -26,10 +26,8 @@ import torch.nn as nn
 
 from . import fused as _fused
 from . import torchpoints as _tp
-from .kpconv_blocks import PDData
 from .partial_dense import MLP
-from .pointnet2_mp import (FPModule, FPSSampler, GlobalBaseModule, PointNet2MP, RadiusNeighbourFinder, _edge_start_of,
-                           _UnetBlock, copy_from_to)
+from .pointnet2_mp import BaseConvolutionDown, FPSSampler, RadiusNeighbourFinder, SegmentationMP, _edge_start_of
 
 
 class Convolution(nn.Module):
@@ -66,7 +64,7 @@ class Convolution(nn.Module):
         return out
 
 
-class RSConvDown(nn.Module):
+class RSConvDown(BaseConvolutionDown):
     """FPSSampler(ratio) + RadiusNeighbourFinder(radius) (at most 64 neighbours, its default) + Convolution(local_nn,
     global_nn=down_conv_nn)."""
 
@@ -76,22 +74,6 @@ class RSConvDown(nn.Module):
         self.neighbour_finder = RadiusNeighbourFinder(radius)
         self._index = kwargs.get("index", None)
         self._conv = Convolution(local_nn=local_nn, global_nn=down_conv_nn, fused=kwargs.get("fused", True))
-
-    def conv(self, x, pos, edge_index, batch):
-        return self._conv(x, pos, edge_index)
-
-    def forward(self, data, **kwargs):
-        out = PDData()
-        x, pos, batch = data.x, data.pos, data.batch
-        idx = self.sampler(pos, batch=batch)
-        out.idx = idx
-        pos_q, batch_q = pos[idx], batch[idx]
-        edges = self.neighbour_finder(pos, pos_q, batch_x=batch, batch_y=batch_q)
-        out.x = self.conv(x, (pos, pos_q), edges, batch)
-        out.pos = pos_q
-        out.batch = batch_q
-        copy_from_to(data, out)
-        return out
 
 
 def rsconv_mp_config(name):
@@ -121,36 +103,16 @@ def rsconv_mp_config(name):
     raise ValueError("unknown message-passing RSConv config %r" % name)
 
 
-class RSConvMP(PointNet2MP):
-    """RSConv_MP segmentation network: RSConvDown x n, GlobalBaseModule, FPModule x (n + 1) and PointNet2MP's head
-    (its forward is inherited).
+class RSConvMP(SegmentationMP):
+    """RSConv_MP segmentation network: SegmentationMP over RSConvDown.
 
-    cfg: "RSConv_2LD" / "RSConv_4LD" (rsconv_mp_config) or a dict with the YAML's fields, numbers already resolved.
-    forward(data) -> log-probabilities (N, num_classes); data carries pos (N,3), a sorted batch (N) and x = None for
-    the two named configurations."""
+    cfg: "RSConv_2LD" / "RSConv_4LD" (rsconv_mp_config) or a dict with the YAML's fields (down_conv: ratios, radius,
+    local_nn, down_conv_nn; the rest as SegmentationMP).  data.x = None for the two named configurations."""
 
     def __init__(self, cfg, num_classes, fused=True):
-        nn.Module.__init__(self)
         if isinstance(cfg, str):
             cfg = rsconv_mp_config(cfg)
-        down, up, inner, head = cfg["down_conv"], cfg["up_conv"], cfg["innermost"], cfg["mlp_cls"]
-        n = len(down["down_conv_nn"])
-        if n + 1 != len(up["up_conv_nn"]):
-            raise ValueError("up_conv_nn must list one module more than down_conv_nn (the innermost block's)")
-
-        def rs(i):
-            return RSConvDown(ratio=down["ratios"][i], radius=down["radius"][i], local_nn=down["local_nn"][i],
-                              down_conv_nn=down["down_conv_nn"][i], index=i, fused=fused)
-
-        def fp(j):
-            return FPModule(up_k=up["up_k"][j], up_conv_nn=up["up_conv_nn"][j], skip=up.get("skip", True), index=j)
-
-        block = _UnetBlock(fp(0), inner=GlobalBaseModule(nn=inner["nn"], aggr=inner.get("aggr", "max")))
-        for index in range(n - 1, -1, -1):
-            block = _UnetBlock(fp(n - index), down=rs(index), submodule=block)
-        self.model = block
-        widths = head["nn"]
-        self.dropout = head.get("dropout")
-        self.lin1 = nn.Linear(widths[0], widths[1])
-        self.lin2 = nn.Linear(widths[2], widths[3])
-        self.lin3 = nn.Linear(widths[4], num_classes)
+        down = cfg["down_conv"]
+        super().__init__(cfg, num_classes, lambda i: RSConvDown(
+            ratio=down["ratios"][i], radius=down["radius"][i], local_nn=down["local_nn"][i],
+            down_conv_nn=down["down_conv_nn"][i], index=i, fused=fused))

@@ -161,6 +161,30 @@ def radius_edges(radius, max_num_neighbors, x, y, batch_x=None, batch_y=None):
     return table_edges(table)
 
 
+def _check_csr(edge_start, col, nq=None, ne=None):
+    """CSR edges: edge_start (Nq + 1,) with Nq = nq where it is known, col (E,) with E = ne where it is known"""
+    if edge_start.dim() != 1 or col.dim() != 1 or edge_start.numel() < 1:
+        raise ValueError("edge_start must be (Nq + 1,) and col (E,)")
+    if nq is not None and edge_start.numel() != nq + 1:
+        raise ValueError("edge_start must have one entry per query plus one")
+    if ne is not None and col.numel() != ne:
+        raise ValueError("col must have one entry per edge row")
+
+
+def _edge_rows_to_support(g, col, M, C, out=None):
+    """dx (M, C) = for every support row the sum of the edge-gradient rows g[e, :C] with col[e] == it (g (E, ld) float32,
+    E > 0): tp3d_rows_scatter_bwd_f32 with B = 1 and no weights (inverse table + ordered gather-sum, no atomics).
+    Every element of dx is written; `out` (M, C) contiguous is filled instead of a new tensor."""
+    dev = g.device
+    E, ld = g.shape
+    dx = torch.empty((M, C), dtype=torch.float32, device=dev) if out is None else out
+    ws, nbytes = _lib.scatter_workspace(1, E, M, False, dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_rows_scatter_bwd_f32", _lib.ptr(g), _lib.ptr(col), None, 1, E, 1, M, ld, 0, C, _lib.ptr(dx),
+                  _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+    return dx
+
+
 class _PointConvRows(torch.autograd.Function):
     """rows (E, ld) = [ x[col] | pos_s[col] - pos_q[query of the edge] | 0 ];  differentiable wrt x."""
 
@@ -181,20 +205,14 @@ class _PointConvRows(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (col,) = ctx.saved_tensors
-        M, C, ld = ctx.cfg
+        M, C, _ = ctx.cfg
         dx = None
         if C and ctx.needs_input_grad[0]:
             g = g.float().contiguous()
-            dev = g.device
-            E = col.shape[0]
-            dx = torch.empty((M, C), dtype=torch.float32, device=dev)
-            if E == 0:
-                dx.zero_()
+            if col.shape[0] == 0:
+                dx = torch.zeros((M, C), dtype=torch.float32, device=g.device)
             else:
-                ws, nbytes = _lib.scatter_workspace(1, E, M, False, dev)
-                with _lib.on_device(dev):
-                    _lib.call("tp3d_rows_scatter_bwd_f32", _lib.ptr(g), _lib.ptr(col), None, 1, E, 1, M, ld, 0, C,
-                              _lib.ptr(dx), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+                dx = _edge_rows_to_support(g, col, M, C)
         return dx, None, None, None, None, None
 
 
@@ -206,8 +224,7 @@ def pointconv_rows(x, pos_s, pos_q, edge_start, col, ld=None):
     ld = ((C + 3 + 3) & ~3) if ld is None else int(ld)
     if ld < C + 3:
         raise ValueError("ld must be at least C + 3")
-    if edge_start.numel() != pos_q.shape[0] + 1:
-        raise ValueError("edge_start must have one entry per query plus one")
+    _check_csr(edge_start, col, nq=pos_q.shape[0])
     return _PointConvRows.apply(x, _f32(pos_s), _f32(pos_q), _i64(edge_start), _i64(col), ld)
 
 
@@ -255,11 +272,6 @@ def segment_max(rows, seg, C=None, return_argmax=False):
     return (out, arg) if return_argmax else out
 
 
-def _check_csr(edge_start, col, nq):
-    if edge_start.dim() != 1 or col.dim() != 1 or edge_start.numel() != nq + 1:
-        raise ValueError("edge_start must have one entry per query plus one, col one per edge")
-
-
 def rsconv_relation_rows(pos_s, pos_q, edge_start, col, ld=None):
     """The relation rows of RSConv, [|d|, d = pos_q[i] - pos_s[j], pos_q[i], pos_s[j]] per edge (j -> i): pos_s (M,3),
     pos_q (Nq,3), CSR edges -> (E, ld) float32, ld >= 10 (default 12: a multiple of 4, zero padded).  No gradient."""
@@ -269,7 +281,7 @@ def rsconv_relation_rows(pos_s, pos_q, edge_start, col, ld=None):
         raise ValueError("ld must be at least 10")
     if pos_s.dim() != 2 or pos_s.shape[1] != 3 or pos_q.dim() != 2 or pos_q.shape[1] != 3:
         raise ValueError("pos_s and pos_q must be (M, 3) and (Nq, 3)")
-    _check_csr(edge_start, col, pos_q.shape[0])
+    _check_csr(edge_start, col, nq=pos_q.shape[0])
     pos_s, pos_q, edge_start, col = _f32(pos_s), _f32(pos_q), _i64(edge_start), _i64(col)
     M, Nq, E = pos_s.shape[0], pos_q.shape[0], col.shape[0]
     out = torch.empty((E, ld), dtype=torch.float32, device=dev)
@@ -322,13 +334,10 @@ class _RSConvMsgMax(torch.autograd.Function):
                 _lib.call("tp3d_rsconv_msgmax_bwd_f32", _lib.ptr(g), _lib.ptr(arg), _lib.ptr(wf), ldw, _lib.ptr(xf), ldx,
                           _lib.ptr(col), _lib.ptr(edge_start), Nq, M, E, C, _lib.ptr(d_w), _lib.ptr(g_x),
                           _lib.stream_ptr(dev))
-                if g_x is not None:
-                    dxc = dx if ldx == C else torch.empty((M, C), dtype=torch.float32, device=dev)
-                    ws, nbytes = _lib.scatter_workspace(1, E, M, False, dev)
-                    _lib.call("tp3d_rows_scatter_bwd_f32", _lib.ptr(g_x), _lib.ptr(col), None, 1, E, 1, M, ldw, 0, C,
-                              _lib.ptr(dxc), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
-                    if dxc is not dx:
-                        dx[:, :C] = dxc
+            if g_x is not None:
+                dxc = _edge_rows_to_support(g_x, col, M, C, out=dx if ldx == C else None)
+                if dxc is not dx:
+                    dx[:, :C] = dxc
         return (d_w if ctx.needs_input_grad[0] else None), dx, None, None, None
 
 
@@ -343,8 +352,7 @@ def rsconv_msgmax(w, x, edge_start, col, C=None, return_argmax=False):
     C = x.shape[1] if C is None else int(C)
     if C < 0 or C > w.shape[1] or C > x.shape[1]:
         raise ValueError("C exceeds the row length of w or x")
-    if edge_start.dim() != 1 or edge_start.numel() < 1 or col.dim() != 1 or col.numel() != w.shape[0]:
-        raise ValueError("edge_start must be (Nq + 1,) and col must have one entry per row of w")
+    _check_csr(edge_start, col, ne=w.shape[0])
     out, arg = _RSConvMsgMax.apply(w, x, _i64(edge_start), _i64(col), C)
     return (out, arg) if return_argmax else out
 
