@@ -576,6 +576,36 @@ int tp3d_rsconv_msgmax_bwd_f32(const float *dout, const int64_t *arg, const floa
                                const int64_t *col, const int64_t *edge_start, int64_t Nq, int64_t M, int64_t E, int C,
                                float *d_w, float *g_x, void *stream);
 
+/* Sparse voxel convolution (csrc/sparseconv.hip)      [modules/SparseConv3d/nn/torchsparse.py, modules/SparseConv3d/modules.py]
+ *   coords (N, 4) int32 rows [x, y, z, batch], |x|, |y|, |z| < 2^18, 0 <= batch < 2^9.
+ *   A coordinate SET is (keys (rows) int64 sorted, rows (rows) int32 = owner row of each sorted slot, meta 16 int32 =
+ *   [min x, y, z | max x, y, z | max batch | bad flags | row count | 0...]); bad flags: 1 = a value out of range, 2 = two equal
+ *   voxels (input set only), 4 = bounding box * batches does not fit the 64-bit key.  The host reads meta once per new set.
+ *   tp3d_sparse_set_build_i32: down == 0: the set of `coords` themselves, rows in the caller's order (keys_out, rows_out: N).
+ *     down > 0: the distinct floor(c / down) * down per axis (batch kept), ascending (batch, x, y, z): keys_out, rows_out
+ *     (= iota) and coords_out (., 4) sized for N rows, meta[8] of them written.
+ *   tp3d_sparse_kmap_i32: table (Nq, ksize^3) int32 = the row of the set's voxel at qcoords[q] + sign * offset_k * step, -1
+ *     where absent; offsets {-1, 0, 1} (ksize 3), {0, 1} (ksize 2), {0} (ksize 1) per axis, x slowest, z fastest.
+ *   tp3d_sparse_kmap_mirror_i32: inverse[i][k] = forward[i][K - 1 - k] (stride 1, odd kernel).
+ *   tp3d_sparse_conv_f32: y (Nout, Cout) = sum_k x[table[r][k]] . W[k], x (Nsrc, Cin); W (K, Cin, Cout), or with
+ *     w_transposed != 0 W is (K, Cout, Cin) and W[k]^T is applied.  An entry outside [0, Nsrc) counts as absent.  fp32
+ *     MFMA over LDS-staged gathered rows; Cin <= 4 plain FMA.  No atomics: bit-reproducible.
+ *   tp3d_sparse_wgrad_f32: dW (K, Cin, Cout) = sum_r x[table[r][k]]^T . dy[r], x (Nsrc, Cin), dy (N, Cout), table (N, K);
+ *     tp3d_sparse_wgrad_chunks(N, K, Cin, Cout) row chunks, each summed in ascending row order, their partials
+ *     (workspace: tp3d_sparse_wgrad_workspace_floats, 0 for one chunk) summed in ascending chunk order. */
+size_t tp3d_sparse_workspace_bytes(int64_t N);
+int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int down, int64_t *keys_out, int32_t *rows_out,
+                              int32_t *coords_out, int32_t *meta, void *workspace, size_t workspace_bytes, void *stream);
+int tp3d_sparse_kmap_i32(const int32_t *qcoords, int64_t Nq, int ksize, int step, int sign, const int64_t *keys,
+                         const int32_t *rows, const int32_t *meta, int64_t Ns, int32_t *table, void *stream);
+int tp3d_sparse_kmap_mirror_i32(const int32_t *forward, int64_t N, int K, int32_t *inverse, void *stream);
+int tp3d_sparse_conv_f32(const float *x, const int32_t *table, const float *W, int64_t Nout, int64_t Nsrc, int K, int Cin,
+                         int Cout, int w_transposed, float *y, void *stream);
+int tp3d_sparse_wgrad_chunks(int64_t N, int K, int Cin, int Cout);
+size_t tp3d_sparse_wgrad_workspace_floats(int64_t N, int K, int Cin, int Cout);
+int tp3d_sparse_wgrad_f32(const float *x, const float *dy, const int32_t *table, int64_t N, int64_t Nsrc, int K, int Cin,
+                          int Cout, float *dW, float *workspace, size_t workspace_floats, void *stream);
+
 /* =====================================================================================================
  * Launch plans (host arithmetic only, no device work): what an entry point WILL do for given sizes -- how it
  * splits the rows, how many partial rows it writes, how it carves its workspace.  tests/test_plans_cpu.py sweeps

@@ -82,6 +82,11 @@ SIGNATURES = {
     "tp3d_rsconv_relation_rows_f32": [_p, _p, _p, _p, _l, _l, _l, _i, _p, _p],
     "tp3d_rsconv_msgmax_fwd_f32": [_p, _i, _p, _i, _p, _p, _l, _l, _l, _i, _p, _p, _p],
     "tp3d_rsconv_msgmax_bwd_f32": [_p, _p, _p, _i, _p, _i, _p, _p, _l, _l, _l, _i, _p, _p, _p],
+    "tp3d_sparse_set_build_i32": [_p, _l, _i, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
+    "tp3d_sparse_kmap_i32": [_p, _l, _i, _i, _i, _p, _p, _p, _l, _p, _p],
+    "tp3d_sparse_kmap_mirror_i32": [_p, _l, _i, _p, _p],
+    "tp3d_sparse_conv_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _i, _p, _p],
+    "tp3d_sparse_wgrad_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
     # launch plans (host arithmetic; the last argument is a HOST int64 array)
     "tp3d_gemm_tn_plan": [_l, _i, _i, _p],
     "tp3d_gemm_tn_x3_plan": [_l, _i, _i, _p],
@@ -115,6 +120,9 @@ MISC = {
     "tp3d_knn_workspace_bytes": (_z, [_i, _l, _i]),
     "tp3d_voxel_workspace_bytes": (_z, [_l]),
     "tp3d_ball_query_workspace_bytes": (_z, [_i, _l, _i]),
+    "tp3d_sparse_workspace_bytes": (_z, [_l]),
+    "tp3d_sparse_wgrad_chunks": (_i, [_l, _i, _i, _i]),
+    "tp3d_sparse_wgrad_workspace_floats": (_z, [_l, _i, _i, _i]),
 }
 ABI_VERSION = 39
 
