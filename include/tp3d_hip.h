@@ -577,11 +577,12 @@ int tp3d_rsconv_msgmax_bwd_f32(const float *dout, const int64_t *arg, const floa
                                float *d_w, float *g_x, void *stream);
 
 /* Sparse voxel convolution (csrc/sparseconv.hip)      [modules/SparseConv3d/nn/torchsparse.py, modules/SparseConv3d/modules.py]
- *   coords (N, 4) int32 rows [x, y, z, batch], |x|, |y|, |z| < 2^18, 0 <= batch < 2^9.
+ *   coords (N, 4) int32 rows [x, y, z, batch], 0 <= batch < 2^9; a voxel of tensor stride ts covers [c, c + ts) per axis and
+ *   is accepted when that holds a coordinate of (-2^18, 2^18): |c| < 2^18 at ts = 1, -2^18 allowed at a coarser stride.
  *   A coordinate SET is (keys (rows) int64 sorted, rows (rows) int32 = owner row of each sorted slot, meta 16 int32 =
  *   [min x, y, z | max x, y, z | max batch | bad flags | row count | 0...]); bad flags: 1 = a value out of range, 2 = two equal
  *   voxels (input set only), 4 = bounding box * batches does not fit the 64-bit key.  The host reads meta once per new set.
- *   tp3d_sparse_set_build_i32: down == 0: the set of `coords` themselves, rows in the caller's order (keys_out, rows_out: N).
+ *   tp3d_sparse_set_build_i32: ts = the tensor stride of `coords` (the range rule above).  down == 0: the set of `coords` themselves, rows in the caller's order (keys_out, rows_out: N).
  *     down > 0: the distinct floor(c / down) * down per axis (batch kept), ascending (batch, x, y, z): keys_out, rows_out
  *     (= iota) and coords_out (., 4) sized for N rows, meta[8] of them written.
  *   tp3d_sparse_kmap_i32: table (Nq, ksize^3) int32 = the row of the set's voxel at qcoords[q] + sign * offset_k * step, -1
@@ -594,7 +595,7 @@ int tp3d_rsconv_msgmax_bwd_f32(const float *dout, const int64_t *arg, const floa
  *     tp3d_sparse_wgrad_chunks(N, K, Cin, Cout) row chunks, each summed in ascending row order, their partials
  *     (workspace: tp3d_sparse_wgrad_workspace_floats, 0 for one chunk) summed in ascending chunk order. */
 size_t tp3d_sparse_workspace_bytes(int64_t N);
-int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int down, int64_t *keys_out, int32_t *rows_out,
+int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int ts, int down, int64_t *keys_out, int32_t *rows_out,
                               int32_t *coords_out, int32_t *meta, void *workspace, size_t workspace_bytes, void *stream);
 int tp3d_sparse_kmap_i32(const int32_t *qcoords, int64_t Nq, int ksize, int step, int sign, const int64_t *keys,
                          const int32_t *rows, const int32_t *meta, int64_t Ns, int32_t *table, void *stream);

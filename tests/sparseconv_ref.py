@@ -6,8 +6,16 @@ Coordinate sets come from torch.unique on floored coordinates; every convolution
     k = 3, stride 1      F.conv3d(stride=1, padding=1)
     k = 3, stride 2      F.conv3d(stride=2, padding=1)
     k = 2, stride 2      F.conv3d(stride=2, padding=0)
+    k = 2, stride 1      F.conv3d(stride=1, padding=0) over the grid with one more zero cell on the high side
+    k = 1, stride 2      F.conv3d(stride=2, padding=0)
     transposed k = 3, 2  F.conv_transpose3d(stride=2, padding=1, output_padding=1)
+    transposed k = 2, 2  F.conv_transpose3d(stride=2, padding=0)
+    transposed k = 1, 2  F.conv_transpose3d(stride=2, padding=0, output_padding=1)
     transposed k = 3, 1  F.conv_transpose3d(stride=1, padding=1)
+    transposed k = 2, 1  F.conv_transpose3d(stride=1, padding=0) (one cell longer on the high side; never read)
+
+`lookup` / `kernel_map` compare rows, not packed keys, so they are exact over the whole accepted range (|x|, |y|, |z| <=
+2^18, 0 <= batch < 2^9 is 66 bits); `conv_by_table` is the same sum over such a table, for clouds too wide for a grid.
 
 Works in fp32 and float64 (the dtype of the features and weights) on any device.  The blocks and networks below restate
 modules/SparseConv3d/modules.py and applications/sparseconv3d.py with the reference's attribute names.
@@ -30,18 +38,24 @@ def offsets(ksize, ts):
     return [(a * ts, b * ts, c * ts) for a in r for b in r for c in r]  # x slowest, z fastest
 
 
-def _keys(c):
-    c = c.long()
-    R = 1 << 20
-    return ((c[:, 3] * R + c[:, 0] + R // 2) * R + c[:, 1] + R // 2) * R + c[:, 2] + R // 2
+def _row_ids(rows):
+    """one int64 per (x, y, z, batch) row, equal exactly where the rows are equal: a mixed-radix key over the rows' own
+    bounding box where that fits 62 bits, else the row's rank among the distinct rows"""
+    lo = rows.min(0).values
+    ext = rows.max(0).values - lo + 1
+    if float(ext.double().prod()) < 2.0 ** 62:
+        d = rows - lo
+        return ((d[:, 3] * ext[0] + d[:, 0]) * ext[1] + d[:, 1]) * ext[2] + d[:, 2]
+    return torch.unique(rows, dim=0, return_inverse=True)[1]
 
 
 def lookup(Cq, off, Cs):
     """row of Cs at Cq + off, -1 where absent"""
-    ks, order = torch.sort(_keys(Cs))
     q = Cq.long().clone()
     q[:, :3] += torch.tensor(off, device=q.device)
-    kq = _keys(q)
+    ids = _row_ids(torch.cat([Cs.long(), q], 0))
+    ks, order = torch.sort(ids[:len(Cs)])
+    kq = ids[len(Cs):]
     pos = torch.searchsorted(ks, kq).clamp(max=ks.numel() - 1)
     return torch.where(ks[pos] == kq, order[pos], torch.full_like(pos, -1))
 
@@ -71,7 +85,7 @@ def _read(g, C, ts, origin):
 def conv(Fx, C_in, C_out, W, ksize, stride, ts, transposed=False):
     """Fx on the rows of its own set; ts = tensor stride of the FINE set (the input of a forward, the output of a
     transposed convolution).  W (k^3, Cin, Cout) or (Cin, Cout)."""
-    if ksize == 1:
+    if ksize == 1 and stride == 1:
         return Fx @ W.reshape(Fx.shape[1], -1)
     cin, cout = W.shape[-2], W.shape[-1]
     Wd = W.reshape(ksize, ksize, ksize, cin, cout)
@@ -84,12 +98,29 @@ def conv(Fx, C_in, C_out, W, ksize, stride, ts, transposed=False):
     n_fine = n_coarse * stride
     if not transposed:
         g = _dense(Fx, C_in, ts, origin, n_fine.tolist(), B)
+        if ksize == 2 and stride == 1:
+            g = F.pad(g, (0, 1, 0, 1, 0, 1))  # offsets {0, 1}: the last cell of every axis reads one past the grid
         out = F.conv3d(g, Wd.permute(4, 3, 0, 1, 2), stride=stride, padding=1 if ksize == 3 else 0)
         return _read(out, C_out, cs, origin)
     g = _dense(Fx, C_in, cs, origin, n_coarse.tolist(), B)
     pad = 1 if ksize == 3 else 0  # (k = 2, stride 2: rows 2j and 2j + 1, no padding on either side)
-    out = F.conv_transpose3d(g, Wd.permute(3, 4, 0, 1, 2), stride=stride, padding=pad, output_padding=(stride - 1) * pad)
+    # the fine grid has stride * n_coarse cells per axis: (n - 1) stride - 2 pad + k + output_padding
+    opad = stride + 2 * pad - ksize if stride > 1 else 0
+    out = F.conv_transpose3d(g, Wd.permute(3, 4, 0, 1, 2), stride=stride, padding=pad, output_padding=opad)
     return _read(out, C_out, ts, origin)
+
+
+def conv_by_table(Fx, table, W):
+    """y[r] = sum_k Fx[table[r, k]] @ W[k] over the entries >= 0, in the dtype of Fx and W; differentiable.  With
+    kernel_map's forward table this is the forward convolution, with the inverse table the transposed one."""
+    K = table.shape[1]
+    W = W.reshape(K, Fx.shape[1], -1)
+    y = torch.zeros((table.shape[0], W.shape[2]), dtype=Fx.dtype, device=Fx.device)
+    for k in range(K):
+        hit = torch.nonzero(table[:, k] >= 0).squeeze(1)
+        if hit.numel():
+            y = y.index_add(0, hit, Fx[table[hit, k].long()] @ W[k])
+    return y
 
 
 # ------------------------------------------------------------------------------------------------ modules and networks

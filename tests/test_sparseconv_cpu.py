@@ -183,3 +183,79 @@ def test_project_blocks_load_the_fixture_state_and_widths_equal_the_json():
             assert mine["innermost"]["nn"] == cfg[name]["innermost"]["nn"]
             assert mine["innermost"]["aggr"] == cfg[name]["innermost"]["aggr"] == "mean"
             assert mine["innermost"]["negative_slope"] == cfg[name]["innermost"]["activation"]["negative_slope"]
+
+
+# ------------------------------------------------------------------------- the restatement over the whole accepted range
+LIM = (1 << 18) - 1
+
+
+def test_lookup_is_exact_over_the_accepted_range():
+    """a fixed 2^20 radix wraps at batch 16 (16 * 2^60 = 2^64); rows are compared instead, so batches 0, 16 and 511 at one
+    (x, y, z) stay three voxels, also next to +-(2^18 - 1) on every axis (66 bits of range: no int64 packing fits)"""
+    near = torch.tensor([[1, 2, 3, 0], [1, 2, 3, 16], [1, 2, 3, 511], [1, 2, 4, 16]]).int()
+    wide = torch.cat([near, torch.tensor([[LIM, LIM, LIM, 511], [-LIM, -LIM, -LIM, 0], [-LIM, LIM, -LIM, 16],
+                                          [LIM - 1, LIM, LIM, 511], [-LIM, -LIM, -LIM + 1, 0]]).int()])
+    for C in (near, wide):  # the bounding-box key, and (wide: 2^66 cells) the distinct-row rank
+        assert ref.lookup(C, (0, 0, 0), C).tolist() == list(range(len(C)))
+        assert ref.lookup(C[:3], (0, 0, 1), C).tolist() == [-1, 3, -1]
+        assert ref.lookup(C[3:4], (0, 0, -1), C).tolist() == [1]
+    assert ref.lookup(wide, (-1, 0, 0), wide).tolist() == [-1, -1, -1, -1, 7, -1, -1, -1, -1]
+    assert ref.lookup(wide, (0, 0, 1), wide).tolist() == [-1, 3, -1, -1, -1, 8, -1, -1, -1]
+    assert ref.lookup(wide, (1, 1, 1), wide).tolist() == [-1] * 9  # steps outside +-(2^18 - 1): absent, no wrap onto a row
+    # a query set that is not the target set, in another order
+    assert ref.lookup(torch.tensor([[-LIM, -LIM, -LIM, 16], [LIM, LIM, LIM - 1, 511], [1, 2, 2, 511]]).int(), (0, 0, 1),
+                      wide).tolist() == [-1, 4, 2]
+    fwd, inv = ref.kernel_map(wide, wide, 3, 1)
+    assert (fwd >= 0).sum(1).tolist() == [1, 2, 1, 2, 2, 2, 1, 2, 2] and torch.equal(inv, fwd.flip(1))
+
+
+ACCEPTED = [(k, stride, tr) for k in (1, 2, 3) for stride in (1, 2) for tr in (False, True)]
+
+
+@pytest.mark.parametrize("ts", [1, 2])
+@pytest.mark.parametrize("k,stride,transposed", ACCEPTED)
+def test_table_convolution_equals_the_dense_one(k, stride, transposed, ts):
+    """conv_by_table over kernel_map == the dense grid convolution in float64 to 1e-12 (observed: below 2e-14), for every
+    (kernel_size, stride, transposed) the project accepts -- k = 2 at stride 1 in both directions included -- on a cloud
+    with negative coordinates, at fine tensor strides 1 and 2"""
+    g = torch.Generator().manual_seed(k * 100 + stride * 10 + ts)
+    C = torch.unique(torch.cat([torch.randint(-7, 6, (160, 3), generator=g), torch.randint(0, 2, (160, 1), generator=g)], 1),
+                     dim=0).int()
+    fine = C if ts == 1 else ref.down_coords(C, ts)
+    assert int(fine[:, :3].min()) < 0 and len(fine) > 60
+    coarse = fine if stride == 1 else ref.down_coords(fine, ts * stride)
+    fwd, inv = ref.kernel_map(fine, coarse, k, ts)
+    assert int((fwd >= 0).sum()) == int((inv >= 0).sum()) > 0
+    C_in, C_out, table = (coarse, fine, inv) if transposed else (fine, coarse, fwd)
+    x = torch.randn(len(C_in), 3, generator=g, dtype=torch.float64, requires_grad=True)
+    W = torch.randn(k ** 3, 3, 5, generator=g, dtype=torch.float64, requires_grad=True)
+    cot = torch.randn(len(C_out), 5, generator=g, dtype=torch.float64)
+    dense = ref.conv(x, C_in, C_out, W, k, stride, ts, transposed)
+    want = torch.autograd.grad((dense * cot).sum(), (x, W))
+    got = ref.conv_by_table(x, table, W)
+    assert got.dtype == torch.float64 and got.shape == (len(C_out), 5)
+    torch.testing.assert_close(got, dense, rtol=1e-12, atol=1e-12)
+    for a, b in zip(torch.autograd.grad((got * cot).sum(), (x, W)), want):
+        torch.testing.assert_close(a, b, rtol=1e-12, atol=1e-12)
+    y32 = ref.conv_by_table(x.detach().float(), table, W.detach().float())
+    assert y32.dtype == torch.float32
+    torch.testing.assert_close(y32.double(), dense.detach(), rtol=1e-4, atol=1e-4)
+
+
+def test_coordinate_rule_is_closed_under_flooring():
+    """one rule: a voxel [c, c + stride) must hold a coordinate of (-2^18, 2^18).  -(2^18 - 1) floors to -2^18,
+    which a stride-2 (and its floor, a stride-4) tensor therefore accepts and a stride-1 tensor does not."""
+    from torch_points3d_amd import sparseconv as sc
+    C = torch.tensor([[-LIM, LIM, 0, 0], [5, -LIM, LIM, 511]]).int()
+    sc.check_coords_host(C, 1)
+    C2 = ref.down_coords(C, 2)
+    assert C2.tolist() == [[-LIM - 1, LIM - 1, 0, 0], [4, -LIM - 1, LIM - 1, 511]]
+    sc.SparseTensor(torch.zeros(2, 1), C2, stride=2)
+    C4 = ref.down_coords(C2, 4)
+    assert int(C4.min()) == -LIM - 1
+    sc.SparseTensor(torch.zeros(2, 1), C4, stride=4)
+    with pytest.raises(ValueError, match="out of range"):
+        sc.SparseTensor(torch.zeros(2, 1), C2, stride=1)
+    for bad, stride in (([-LIM - 3, 0, 0, 0], 2), ([0, LIM + 1, 0, 0], 2), ([0, 0, -LIM - 5, 0], 4), ([0, 0, LIM + 1, 0], 4)):
+        with pytest.raises(ValueError, match="out of range"):
+            sc.SparseTensor(torch.zeros(1, 1), torch.tensor([bad]).int(), stride=stride)

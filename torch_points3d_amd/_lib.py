@@ -82,7 +82,7 @@ SIGNATURES = {
     "tp3d_rsconv_relation_rows_f32": [_p, _p, _p, _p, _l, _l, _l, _i, _p, _p],
     "tp3d_rsconv_msgmax_fwd_f32": [_p, _i, _p, _i, _p, _p, _l, _l, _l, _i, _p, _p, _p],
     "tp3d_rsconv_msgmax_bwd_f32": [_p, _p, _p, _i, _p, _i, _p, _p, _l, _l, _l, _i, _p, _p, _p],
-    "tp3d_sparse_set_build_i32": [_p, _l, _i, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
+    "tp3d_sparse_set_build_i32": [_p, _l, _i, _i, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
     "tp3d_sparse_kmap_i32": [_p, _l, _i, _i, _i, _p, _p, _p, _l, _p, _p],
     "tp3d_sparse_kmap_mirror_i32": [_p, _l, _i, _p, _p],
     "tp3d_sparse_conv_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _i, _p, _p],

@@ -21,7 +21,7 @@
 namespace tp3d {
 
 constexpr int SP_BLOCK = 256;
-constexpr int SP_COORD_LIMIT = 1 << 18;  // |coord| below this
+constexpr int SP_COORD_LIMIT = 1 << 18;  // |coord| below this at tensor stride 1
 constexpr int SP_BATCH_LIMIT = 1 << 9;   // batch below this
 constexpr int SP_META = 16;
 constexpr int SP_BAD_RANGE = 1, SP_BAD_DUP = 2, SP_BAD_SPAN = 4;
@@ -36,6 +36,11 @@ __device__ __forceinline__ int sp_floor_to(int c, int m)
     return q * m;
 }
 
+// The one coordinate rule (sparseconv.py check_coords_host): a voxel of tensor stride ts covers [c, c + ts) per
+// axis and is accepted when that interval holds a coordinate of (-2^18, 2^18).  At ts = 1 that is |c| < 2^18; a coarser
+// set may hold -2^18 itself, the floor of -(2^18 - 1), so the floor of an accepted voxel is accepted at the coarser stride.
+__device__ __forceinline__ bool sp_coord_ok(int c, int ts) { return c < SP_COORD_LIMIT && c > -SP_COORD_LIMIT - ts + 1; }
+
 __global__ void sp_meta_init_kernel(int *meta)
 {
     const int t = threadIdx.x;
@@ -45,7 +50,7 @@ __global__ void sp_meta_init_kernel(int *meta)
 }
 
 // bounding box of the (floored) coordinates + the range flag
-__global__ __launch_bounds__(SP_BLOCK) void sp_bounds_kernel(const int *__restrict__ coords, int64_t N, int down,
+__global__ __launch_bounds__(SP_BLOCK) void sp_bounds_kernel(const int *__restrict__ coords, int64_t N, int ts, int down,
                                                               int *__restrict__ meta)
 {
     __shared__ int s_red[8][SP_BLOCK / 64];
@@ -54,7 +59,7 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_bounds_kernel(const int *__restri
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             int c = coords[i * 4 + a];
-            if (c <= -SP_COORD_LIMIT || c >= SP_COORD_LIMIT) {
+            if (!sp_coord_ok(c, ts)) {
                 v[7] |= SP_BAD_RANGE;
                 c = 0;
             }
@@ -105,13 +110,13 @@ __device__ __forceinline__ bool sp_key(const int *__restrict__ meta, int x, int 
     return true;
 }
 
-__global__ __launch_bounds__(SP_BLOCK) void sp_key_kernel(const int *__restrict__ coords, int64_t N, int down,
+__global__ __launch_bounds__(SP_BLOCK) void sp_key_kernel(const int *__restrict__ coords, int64_t N, int ts, int down,
                                                            int *__restrict__ meta, unsigned long long *__restrict__ keys,
                                                            unsigned int *__restrict__ vals)
 {
     const int64_t i = (int64_t)blockIdx.x * SP_BLOCK + threadIdx.x;
     if (i == 0) {
-        // extents < 2^19 each, batches <= 2^9: the product may pass 2^63 only for a box no real scene has -- flag it
+        // extents <= 2^19 each, batches <= 2^9: the product may pass 2^63 only for a box no real scene has -- flag it
         const double total = ((double)meta[3] - meta[0] + 1.0) * ((double)meta[4] - meta[1] + 1.0) *
                              ((double)meta[5] - meta[2] + 1.0) * ((double)meta[6] + 1.0);
         if (total >= 4.0e18) atomicOr(&meta[7], SP_BAD_SPAN);
@@ -121,7 +126,7 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_key_kernel(const int *__restrict_
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         c[a] = coords[i * 4 + a];
-        if (c[a] <= -SP_COORD_LIMIT || c[a] >= SP_COORD_LIMIT) c[a] = 0;  // (flagged by the bounds pass)
+        if (!sp_coord_ok(c[a], ts)) c[a] = 0;  // (flagged by the bounds pass)
         if (down > 0) c[a] = sp_floor_to(c[a], down);
     }
     int b = coords[i * 4 + 3];
@@ -156,7 +161,8 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_flag_kernel(const unsigned long l
 __global__ __launch_bounds__(SP_BLOCK) void sp_compact_kernel(const unsigned long long *__restrict__ keys,
                                                                const unsigned int *__restrict__ vals,
                                                                const int *__restrict__ cid, const int *__restrict__ coords,
-                                                               int64_t N, int down, unsigned long long *__restrict__ keys_out,
+                                                               int64_t N, int ts, int down,
+                                                               unsigned long long *__restrict__ keys_out,
                                                                int *__restrict__ rows_out, int *__restrict__ coords_out,
                                                                int *__restrict__ meta)
 {
@@ -170,7 +176,7 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_compact_kernel(const unsigned lon
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             int v = coords[p * 4 + a];
-            if (v <= -SP_COORD_LIMIT || v >= SP_COORD_LIMIT) v = 0;
+            if (!sp_coord_ok(v, ts)) v = 0;
             coords_out[(int64_t)c * 4 + a] = sp_floor_to(v, down);
         }
         coords_out[(int64_t)c * 4 + 3] = coords[p * 4 + 3];
@@ -477,11 +483,11 @@ TP3D_EXPORT size_t tp3d_sparse_workspace_bytes(int64_t N)
     return carve_sparse_workspace(nullptr, N).bytes;
 }
 
-TP3D_EXPORT int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int down, int64_t *keys_out, int32_t *rows_out,
-                                          int32_t *coords_out, int32_t *meta, void *workspace, size_t workspace_bytes,
-                                          void *stream)
+TP3D_EXPORT int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int ts, int down, int64_t *keys_out,
+                                          int32_t *rows_out, int32_t *coords_out, int32_t *meta, void *workspace,
+                                          size_t workspace_bytes, void *stream)
 {
-    if (N <= 0 || N >= 0x7fffffff || down < 0 || down >= SP_COORD_LIMIT || !coords || !keys_out || !rows_out || !meta ||
+    if (N <= 0 || N >= 0x7fffffff || ts < 1 || ts >= SP_COORD_LIMIT || down < 0 || down >= SP_COORD_LIMIT || !coords || !keys_out || !rows_out || !meta ||
         !workspace || (down > 0 && !coords_out))
         return TP3D_E_BADARG;
     SparseWorkspace w = carve_sparse_workspace(workspace, N);
@@ -490,9 +496,10 @@ TP3D_EXPORT int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int 
     const unsigned blocks = (unsigned)((N + SP_BLOCK - 1) / SP_BLOCK);
     hipLaunchKernelGGL(sp_meta_init_kernel, dim3(1), dim3(64), 0, s, meta);
     if (int rc = check_launch()) return rc;
-    hipLaunchKernelGGL(sp_bounds_kernel, dim3(blocks > 1024 ? 1024 : blocks), dim3(SP_BLOCK), 0, s, coords, N, down, meta);
+    hipLaunchKernelGGL(sp_bounds_kernel, dim3(blocks > 1024 ? 1024 : blocks), dim3(SP_BLOCK), 0, s, coords, N, ts, down, meta);
     if (int rc = check_launch()) return rc;
-    hipLaunchKernelGGL(sp_key_kernel, dim3(blocks), dim3(SP_BLOCK), 0, s, coords, N, down, meta, w.keys_in, w.vals_in);
+    hipLaunchKernelGGL(sp_key_kernel, dim3(blocks), dim3(SP_BLOCK), 0, s, coords, N, ts, down, meta, w.keys_in,
+                       w.vals_in);
     if (int rc = check_launch()) return rc;
     unsigned long long *sorted = down > 0 ? w.keys_out : reinterpret_cast<unsigned long long *>(keys_out);
     if (int rc = sort_pairs_u64_u32(w.tmp, w.tmp_bytes, w.keys_in, sorted, w.vals_in, w.vals_out, N, SP_KEY_BITS, s)) return rc;
@@ -505,7 +512,7 @@ TP3D_EXPORT int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int 
     size_t tb = w.tmp_bytes;
     if (int rc = sp_hip_rc(rocprim::inclusive_scan(w.tmp, tb, (const int *)w.flags, w.cid, (size_t)N, rocprim::plus<int>(), s)))
         return rc;
-    hipLaunchKernelGGL(sp_compact_kernel, dim3(blocks), dim3(SP_BLOCK), 0, s, sorted, w.vals_out, w.cid, coords, N, down,
+    hipLaunchKernelGGL(sp_compact_kernel, dim3(blocks), dim3(SP_BLOCK), 0, s, sorted, w.vals_out, w.cid, coords, N, ts, down,
                        reinterpret_cast<unsigned long long *>(keys_out), rows_out, coords_out, meta);
     return check_launch();
 }

@@ -25,14 +25,15 @@ from . import fused as _fused
 from .kpconv import _require_gpu
 from .kpconv_blocks import FastBatchNorm1d
 
-COORD_LIMIT = 1 << 18  # |x|, |y|, |z| below this
+COORD_LIMIT = 1 << 18  # |x|, |y|, |z| below this at tensor stride 1
 BATCH_LIMIT = 1 << 9   # batch index below this
 _BAD_RANGE, _BAD_DUP, _BAD_SPAN = 1, 2, 4
 
 
 def _raise_bad(flags):
     if flags & _BAD_RANGE:
-        raise ValueError("sparse coordinates out of range: need |x|, |y|, |z| < 2^18 and 0 <= batch < 2^9")
+        raise ValueError("sparse coordinates out of range: need 0 <= batch < 2^9 and every voxel [c, c + tensor stride) to "
+                         "hold a coordinate with |x|, |y|, |z| < 2^18")
     if flags & _BAD_SPAN:
         raise ValueError("sparse coordinates span too large a box: extent_x * extent_y * extent_z * batches must stay "
                          "below 2^62")
@@ -40,12 +41,16 @@ def _raise_bad(flags):
         raise ValueError("duplicate coordinates in a sparse tensor: every (x, y, z, batch) row must be distinct")
 
 
-def check_coords_host(coords):
-    """The accepted-input rule on a host tensor (what the device build flags in its read-back)."""
+def check_coords_host(coords, stride=1):
+    """The accepted-input rule on a host tensor (what the device build flags in its read-back): a voxel of tensor stride
+    `stride` covers [c, c + stride) per axis and must hold a coordinate of (-2^18, 2^18) -- |c| < 2^18 at stride 1, and
+    -2^18 itself (the floor of -(2^18 - 1)) at a coarser one."""
     c = coords.long()
     flags = 0
     if c.numel():
-        if bool((c[:, :3].abs() >= COORD_LIMIT).any()) or bool((c[:, 3] < 0).any()) or bool((c[:, 3] >= BATCH_LIMIT).any()):
+        xyz = c[:, :3]
+        if (bool((xyz >= COORD_LIMIT).any()) or bool((xyz + stride - 1 <= -COORD_LIMIT).any()) or bool((c[:, 3] < 0).any())
+                or bool((c[:, 3] >= BATCH_LIMIT).any())):
             flags |= _BAD_RANGE
         elif torch.unique(c, dim=0).shape[0] != c.shape[0]:
             flags |= _BAD_DUP
@@ -61,8 +66,8 @@ class _CoordSet(object):
         self.coords, self.keys, self.rows, self.meta, self.n = coords, keys, rows, meta, n
 
 
-def _build_set(coords, down):
-    """down == 0: the set of `coords`; else the distinct floor(c / down) * down, ascending (batch, x, y, z)."""
+def _build_set(coords, ts, down):
+    """`coords` of tensor stride ts.  down == 0: their set; else the distinct floor(c / down) * down, ascending (batch, x, y, z)."""
     dev = coords.device
     N = coords.shape[0]
     if N == 0:
@@ -74,7 +79,7 @@ def _build_set(coords, down):
     nbytes = _lib.load().tp3d_sparse_workspace_bytes(N)
     ws = _lib.workspace("sparse_set", nbytes, dev)
     with _lib.on_device(dev):
-        _lib.call("tp3d_sparse_set_build_i32", _lib.ptr(coords), N, int(down), _lib.ptr(keys), _lib.ptr(rows),
+        _lib.call("tp3d_sparse_set_build_i32", _lib.ptr(coords), N, int(ts), int(down), _lib.ptr(keys), _lib.ptr(rows),
                   _lib.ptr(out_coords), _lib.ptr(meta), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
     host = meta.cpu()  # the one read of a new set: row count and bad-input flags
     _raise_bad(int(host[7]))
@@ -129,7 +134,7 @@ class SparseTensor(object):
         self.cmaps = {} if cmaps is None else cmaps
         self.kmaps = {} if kmaps is None else kmaps
         if cmaps is None and self.C.device.type != "cuda":
-            check_coords_host(self.C)
+            check_coords_host(self.C, self.s)
 
     def to(self, device):
         device = torch.device(device)
@@ -148,7 +153,7 @@ class SparseTensor(object):
         cs = self.cmaps.get(ts)
         if cs is None and ts == self.s:
             _require_gpu(self.C)
-            cs = self.cmaps[ts] = _build_set(self.C.contiguous(), 0)
+            cs = self.cmaps[ts] = _build_set(self.C.contiguous(), ts, 0)
         return cs
 
     def _kmap(self, ksize, ts, stride):
@@ -167,7 +172,7 @@ class SparseTensor(object):
                 if out_set is None:
                     if ts != self.s:
                         raise RuntimeError("no coordinate set of tensor stride %d" % (ts * stride))
-                    out_set = self.cmaps[ts * stride] = _build_set(in_set.coords, ts * stride)
+                    out_set = self.cmaps[ts * stride] = _build_set(in_set.coords, ts, ts * stride)
             km = self.kmaps[key] = _build_kmap(in_set, out_set, ksize, ts, stride == 1)
         return km
 
