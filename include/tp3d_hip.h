@@ -473,7 +473,10 @@ int tp3d_attn_pool_bwd_f32(const float *g, const float *f, const float *dout, co
 
 /* Skinny row GEMM of the edge-wise MLPs (modules/RandLANet/modules.py:20-22; nn.Linear inside MLP,
  * core/common_modules/base_modules.py:29-43):  Y (M, N) = A (M, K; row stride lda >= K) * W (N, K)^T,  N, K <= 32.
- * One row per lane, k ascending per output.  Y is dense (row stride N). */
+ * One row per lane, k ascending per output.  Y is dense (row stride N).
+ * With lda a multiple of 4 and A 16-byte aligned the rows are read as whole float4: the columns [K, pad4(K)) of A are
+ * then read and meet a zero weight, so they must hold finite values (producers write zeros); columns from pad4(K) on are
+ * never read.  Any other lda / alignment reads exactly the K columns. */
 int tp3d_gemm_skinny_f32(const float *A, const float *W, int64_t M, int N, int K, int lda, float *Y, void *stream);
 /* The same with BatchNorm (given statistics rows mean / scale / beta of N: eval mode) and LeakyReLU applied to every
  * output before it is stored: one pass over the rows instead of three (Linear, affine, activation). */

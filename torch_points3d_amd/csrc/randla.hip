@@ -167,6 +167,16 @@ __global__ __launch_bounds__(256) void attn_pool_bwd_kernel(const float *__restr
     }
 }
 
+// df columns [from, ldf) of every edge row = 0: the padding a narrow lane layout (P < 64) leaves beyond its 4 * P columns
+__global__ __launch_bounds__(256) void attn_df_tail_kernel(float *__restrict__ df, int64_t E, int ldf, int from)
+{
+    const int w = ldf - from;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= E * w) return;
+    const int64_t e = t / w;
+    df[e * ldf + from + (int)(t - e * w)] = 0.0f;
+}
+
 struct AttnPlan {
     int P, R;
 };
@@ -235,6 +245,13 @@ TP3D_EXPORT int tp3d_attn_pool_bwd_f32(const float *g, const float *f, const flo
     AttnPlan p = attn_plan(C, ldf);
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((unsigned)((Nq + 3) / 4));
+    // the pooling kernel holds at most 4 channels per lane: with C <= 32 (P < 64) a row wider than 4 * P has padding
+    // columns beyond its reach, cleared by a launch of their own (never the case for ldf = pad4(C))
+    const int tail = p.R > 4 ? 4 * p.P : ldf;
+    const int64_t tail_blocks = (Nq * k * (ldf - tail) + 255) / 256;
+    if (tail_blocks > 0x7fffffffLL) return TP3D_E_TOOBIG;
     TP3D_ATTN_DISPATCH(attn_pool_bwd_kernel, g, f, dout, nbr, Nq, k, C, ldg, ldf, p.P, dg, df)
+    if (tail_blocks)
+        hipLaunchKernelGGL(attn_df_tail_kernel, dim3((unsigned)tail_blocks), dim3(256), 0, s, df, Nq * k, ldf, tail);
     return check_launch();
 }

@@ -8,7 +8,8 @@ neighbour feature, softmax attention over channels, sum over the k neighbours, g
 
 The reference runs this as a torch_geometric MessagePassing over an edge list built by torch_cluster's `knn`; here the
 neighbour table (Nq, k) comes from libtp3d_hip.so's exact grid kNN and, because every query owns exactly k consecutive
-edges, the "add" aggregation is a sum over a (Nq, k, C) view -- no scatter.  Parity: unpinned (torch_cluster absent;
+edges, the "add" aggregation is a sum over a (Nq, k, C) view -- no scatter.  A table with -1 slots (a cloud smaller
+than k) is compacted to its real edges first (`RandlaKernel._forward_ragged`).  Parity: unpinned (torch_cluster absent;
 the reference's own model test skips randlanet, test/test_models.py:116-125).
 """
 import math
@@ -111,9 +112,12 @@ class RandlaKernel(nn.Module):
         self.fused = kwargs.get("fused", True)
 
     def forward(self, x, pos, nbr):
-        """x (M,C) or None, pos = (query positions (Nq,3), support positions (M,3)), nbr (Nq,k) rows of the support"""
+        """x (M,C) or None, pos = (query positions (Nq,3), support positions (M,3)), nbr (Nq,k) rows of the support;
+        -1 slots (a cloud with fewer than k points) are edges that do not exist"""
         pos_q, pos_s = pos
         Nq, k = nbr.shape
+        if bool((nbr < 0).any()):  # one host read per forward
+            return self._forward_ragged(x, pos_q, pos_s, nbr)
         if pos_s.is_cuda and self.fused:
             return self._forward_fused(x, pos_q, pos_s, nbr)
         j = nbr.reshape(-1)
@@ -127,6 +131,34 @@ class RandlaKernel(nn.Module):
         s_ij = F.softmax(_fused.rows_mlp(self.attention_nn, fij_hat), -1)
         msg = s_ij * fij_hat
         return _fused.rows_mlp(self.global_nn, msg.reshape(Nq, k, -1).sum(dim=1))
+
+    def _forward_ragged(self, x, pos_q, pos_s, nbr):
+        """A table with -1 slots: the edge rows are compacted to the real edges first -- the reference's kNN edge list,
+        so the BatchNorms of the edge-wise MLPs see what they see there -- and the messages go back into a zero
+        (Nq*k, C) buffer, summed per query in slot order (one writer per row: deterministic)."""
+        Nq, k = nbr.shape
+        flat = _tp._i64(nbr).reshape(-1)
+        real = torch.nonzero(flat >= 0).reshape(-1)
+        j = flat[real]
+        pos_i = pos_q[torch.div(real, k, rounding_mode="floor")]
+        if pos_s.is_cuda and self.fused:
+            edges = j.reshape(-1, 1)  # every real edge as a query of its own with one neighbour
+            rij = _fused.rows_mlp(self.point_pos_nn, relative_position_rows(pos_i, pos_s, edges))
+            xs = _tp._f32(pos_s) if x is None else x
+            C = xs.shape[1] + rij.shape[1]
+            ones = torch.ones((edges.shape[0], 1), dtype=torch.float32, device=nbr.device)
+            fij_hat = _KnnInterpolate.apply(xs, rij, edges, ones, (C + 3) // 4 * 4)
+            msg = F.softmax(_fused.rows_mlp(self.attention_nn, fij_hat), -1) * fij_hat[:, :C]
+        else:
+            pos_j = pos_s[j]
+            x_j = pos_j if x is None else x[j]
+            vij = pos_i - pos_j
+            dij = torch.norm(vij, dim=1).unsqueeze(1)
+            rij = _fused.rows_mlp(self.point_pos_nn, torch.cat([pos_i, pos_j, vij, dij], dim=1))
+            fij_hat = torch.cat([x_j, rij], dim=1)
+            msg = F.softmax(_fused.rows_mlp(self.attention_nn, fij_hat), -1) * fij_hat
+        rows = msg.new_zeros((Nq * k, msg.shape[1])).index_copy(0, real, msg)
+        return _fused.rows_mlp(self.global_nn, rows.reshape(Nq, k, -1).sum(dim=1))
 
     def _forward_fused(self, x, pos_q, pos_s, nbr):
         """Same arithmetic; the edge-wise pieces between the MLPs are HIP row kernels (csrc/randla.hip) and the
