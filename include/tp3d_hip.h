@@ -610,6 +610,36 @@ size_t tp3d_sparse_wgrad_workspace_floats(int64_t N, int K, int Cin, int Cout);
 int tp3d_sparse_wgrad_f32(const float *x, const float *dy, const int32_t *table, int64_t N, int64_t Nsrc, int K, int Cin,
                           int Cout, float *dW, float *workspace, size_t workspace_floats, void *stream);
 
+/* Point-voxel operations of PVCNN (csrc/pointvoxel.hip)                                     [modules/PVCNN/utils.py]
+ *   Features fp32, tables int32, -1 = absent; an index outside its row range counts as absent.  No float atomics: every
+ *   result is bit-reproducible.  The lookups are tp3d_sparse_kmap_i32 over the coordinates of tp3d_pv_quantize_f32
+ *   (ksize 1: the point's voxel row; ksize 2, step s, sign 1: the 8 corner rows, x slowest, z fastest).
+ *   tp3d_pv_quantize_f32: pc (N, 4) = [x, y, z, batch] -> q (N, 4) int32 = [floor(x / s) * s, ..., (int)batch]; division
+ *     and floor in fp32 (floor, not truncation), s >= 1.
+ *   tp3d_pv_trilinear_f32: w (N, 8); corner k = 4 dx + 2 dy + dz: w = a_x a_y a_z with a = (pf + s) - p (d = 0) or p - pf
+ *     (d = 1), pf = floor(p / s) * s; then / s^3; then 0 where idx8[p][k] is absent (outside [0, Nv)); then
+ *     / (sum_k w + 1e-8); all fp32 in that order.  nearest != 0: afterwards corners 1..7 get w = 0 and idx8 = -1 (written
+ *     to idx8), no renormalisation.
+ *   tp3d_pv_invert_i32: table (N, K), K = 1 or 8, into Nv rows -> start (Nv + 1), order (N * K ints, the first start[Nv]
+ *     written): order[start[v] .. start[v + 1]) = the slots l = p * K + k with table[l] == v in ascending l (stable radix
+ *     sort); absent slots are dropped.  workspace: tp3d_pv_invert_workspace_bytes(N, K).
+ *   tp3d_pv_gather_f32: out (N, C): out[p] = sum_k wk * src[table[p][k]] over the present slots, k ascending; wk =
+ *     w[p][k], or with w NULL scale[table[p][k]], or 1 with both NULL.  src (Nsrc, C).
+ *   tp3d_pv_runsum_f32: out (Nv, C): out[v] = scale[v] * sum over l in order[start[v] .. start[v + 1]) of w[l] *
+ *     src[l / K]; w (Nsrc * K) and scale (Nv) may each be NULL (= 1); src (Nsrc, C); an empty run gives zeros.  A run of
+ *     more than 64 slots is summed in 16 contiguous pieces of ceil(n / 16) slots, each in ascending order, the pieces
+ *     added in order (fixed association by run length: reproducible, not the sequential sum bit for bit).
+ *   Lanes run across channels, float4 where C % 4 == 0 and src / out are 16-byte aligned. */
+int tp3d_pv_quantize_f32(const float *pc, int64_t N, int s, int32_t *q, void *stream);
+int tp3d_pv_trilinear_f32(const float *pc, int32_t *idx8, int64_t N, int64_t Nv, int s, int nearest, float *w, void *stream);
+size_t tp3d_pv_invert_workspace_bytes(int64_t N, int K);
+int tp3d_pv_invert_i32(const int32_t *table, int64_t N, int K, int64_t Nv, int32_t *start, int32_t *order, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int tp3d_pv_gather_f32(const float *src, const int32_t *table, const float *w, const float *scale, int64_t N, int K,
+                       int64_t Nsrc, int C, float *out, void *stream);
+int tp3d_pv_runsum_f32(const float *src, const int32_t *start, const int32_t *order, const float *w, const float *scale,
+                       int64_t Nv, int K, int64_t Nsrc, int C, float *out, void *stream);
+
 /* =====================================================================================================
  * Launch plans (host arithmetic only, no device work): what an entry point WILL do for given sizes -- how it
  * splits the rows, how many partial rows it writes, how it carves its workspace.  tests/test_plans_cpu.py sweeps

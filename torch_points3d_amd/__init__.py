@@ -24,5 +24,12 @@ from .pointnet2_mp import (  # noqa: F401
     RadiusNeighbourFinder,
     SAModule,
 )
+from .pvcnn import (  # noqa: F401  (the factory `pvcnn.pvcnn` stays in its module: the name is the module's)
+    PVCNN,
+    PointTensor,
+    initial_voxelize,
+    point_to_voxel,
+    voxel_to_point,
+)
 
 __version__ = "0.1.0"
