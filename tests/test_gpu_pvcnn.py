@@ -101,6 +101,35 @@ def test_tables_equal_the_restatement(s, nearest):
         assert torch.equal(start.long(), torch.searchsorted(dest, torch.arange(len(c["Cs"]) + 1, device=DEV)))
 
 
+def _inverted_matches_the_restatement(table, Nv):
+    from torch_points3d_amd import pvcnn as pv
+    start, order = pv._invert(table, Nv)
+    flat = table.reshape(-1).long()
+    slots = torch.nonzero((flat >= 0) & (flat < Nv)).squeeze(1)
+    dest, perm = torch.sort(flat[slots], stable=True)
+    assert start.shape == (Nv + 1,) and order.shape == (flat.numel(),)
+    assert int(start[-1]) == len(slots) and int(start[0]) == 0
+    assert torch.equal(order[:len(slots)].long(), slots[perm])
+    assert torch.equal(start.long(), torch.searchsorted(dest, torch.arange(Nv + 1, device=DEV)))
+    return start
+
+
+@pytest.mark.parametrize("Nv", [1, 5])
+@pytest.mark.parametrize("N,K", [(1, 1), (1, 8), (256, 1), (257, 1), (32, 8), (33, 8)])
+def test_invert_at_block_seams_with_absent_and_out_of_range_slots(N, K, Nv):
+    """tp3d_pv_invert_i32 alone: one slot, one workgroup of 256 slots exactly and one slot past it, for both table widths;
+    -1 and the out-of-range row Nv + 3 both count as absent."""
+    g = torch.Generator().manual_seed(1000 * N + 10 * K + Nv)
+    values = torch.tensor([-1] + list(range(Nv)) + [Nv + 3], dtype=torch.int32)
+    table = values[torch.randint(0, len(values), (N, K), generator=g)].to(DEV)
+    _inverted_matches_the_restatement(table, Nv)
+
+
+def test_invert_of_a_table_without_a_present_slot():
+    start = _inverted_matches_the_restatement(torch.full((33, 8), -1, dtype=torch.int32, device=DEV), 5)
+    assert torch.equal(start, torch.zeros(6, dtype=torch.int32, device=DEV))
+
+
 def test_initial_voxelize_builds_the_voxel_set():
     from torch_points3d_amd import pvcnn as pv
     c = _case(1)

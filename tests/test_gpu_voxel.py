@@ -22,7 +22,9 @@ def cloud(n, clouds, seed, scale=1.0):
 
 
 @pytest.mark.parametrize("n,clouds,size", [(1, 1, 0.1), (5, 1, 0.04), (1000, 1, 0.05), (4096, 3, 0.03), (65536, 1, 0.04),
-                                           (65536, 4, 0.02), (300000, 2, 0.01), (20000, 1, 10.0), (777, 5, 1e-3)])
+                                           (65536, 4, 0.02), (300000, 2, 0.01), (20000, 1, 10.0), (777, 5, 1e-3),
+                                           (524289, 2, 0.01),  # one point past 2048 blocks x 256: the bounds pass strides
+                                           (257, 1, 0.2)])     # one slot in a second workgroup, runs across the seam
 def test_cluster_matches_oracle(n, clouds, size):
     from torch_points3d_amd import grid_sampling as gs
     pos, batch = cloud(n, clouds, n + clouds)

@@ -1,10 +1,10 @@
 // Uniform grid over the support points of each cloud: shared by the radius search (grid.hip) and the exact kNN
 // (knn.hip).  Two builders fill the same tables:
 //   * clouds of <= 65536 points: one workgroup per cloud, everything in LDS (grid.hip: grid_build_kernel);
-//   * larger clouds: bounding box with atomics -> (cloud, cell) keys -> one rocPRIM radix sort -> binary-searched
-//     cell starts (grid.hip: gridg_* kernels); any cloud size, any number of workgroups.
+//   * larger clouds: bounding box with atomics -> (cloud, cell) keys -> the radix sort of the sorted-key core
+//     (sorted_keys.h) -> binary-searched cell starts (grid.hip: gridg_* kernels); any cloud size, any number of workgroups.
 #pragma once
-#include "tp3d_common.h"
+#include "sorted_keys.h"
 
 namespace tp3d {
 
@@ -34,11 +34,8 @@ struct GridWorkspace {
     float4 *sorted_pt; // [rows] cell-ordered copy of the points: (x, y, z, cloud-local point id as int bits) --
                        // one 16-byte load per candidate in the query kernels
     // sort-based build only
-    int *bbox;                              // [clouds][6] order-preserving int images of min/max
-    unsigned long long *keys_in, *keys_out; // [rows]
-    unsigned int *vals_in, *vals_out;       // [rows]
-    void *sort_tmp;
-    size_t sort_tmp_bytes;
+    int *bbox;           // [clouds][6] order-preserving int images of min/max
+    SortWorkspace sort;  // (cloud, cell) keys and global rows, [rows] each
     size_t bytes;
 };
 GridWorkspace carve_grid_workspace(void *ws, int num_clouds, int64_t rows, GridPlan plan);
@@ -47,11 +44,6 @@ GridWorkspace carve_grid_workspace(void *ws, int num_clouds, int64_t rows, GridP
 // edge wanted (the search radius for ball queries); <= 0 lets the kernel pick one for `target` points per cell.
 int grid_build(const float *x, const int64_t *seg, int num_clouds, int64_t rows, int N, int Lmax, float cell, float target,
                GridPlan plan, const GridWorkspace &w, hipStream_t s);
-
-// voxel.hip: the one rocPRIM radix sort instantiation of the library (u64 keys, u32 values, stable)
-size_t sort_pairs_tmp_bytes(int64_t n);
-int sort_pairs_u64_u32(void *tmp, size_t tmp_bytes, const unsigned long long *keys_in, unsigned long long *keys_out,
-                       const unsigned int *vals_in, unsigned int *vals_out, int64_t n, unsigned bits, hipStream_t s);
 
 int grid_knn(const float *x, const float *y, const int64_t *seg, const int64_t *batch_y, int num_clouds, int64_t rows,
              int N, int np, int64_t total_q, int Lmax, int k, float cell, int64_t *idx, float *dist2, void *workspace,

@@ -676,13 +676,7 @@ __global__ __launch_bounds__(GG_BLOCK) void gridg_cellstart_kernel(const int64_t
     const int64_t lo = seg ? seg[b] : (int64_t)b * N;
     const int L = seg ? (int)(seg[b + 1] - seg[b]) : N;
     const unsigned long long want = (unsigned long long)b * (unsigned long long)(G * G * G) + (unsigned long long)c;
-    int a = 0, z = L;  // lower bound in keys[lo, lo + L)
-    while (a < z) {
-        const int m = (a + z) >> 1;
-        if (keys[lo + m] < want) a = m + 1;
-        else z = m;
-    }
-    cell_start[(size_t)b * ((size_t)G * G * G + 1) + c] = a;
+    cell_start[(size_t)b * ((size_t)G * G * G + 1) + c] = (int)lower_bound_u64(keys + lo, L, want);
 }
 
 constexpr size_t GRID_LDS_BUDGET = 144 * 1024;
@@ -730,24 +724,12 @@ GridWorkspace carve_grid_workspace(void *ws, int num_clouds, int64_t rows, GridP
     w.sorted_pt = reinterpret_cast<float4 *>(p + off);
     off += up((size_t)rows * 16);
     w.bbox = nullptr;
-    w.keys_in = w.keys_out = nullptr;
-    w.vals_in = w.vals_out = nullptr;
-    w.sort_tmp = nullptr;
-    w.sort_tmp_bytes = 0;
+    w.sort = SortWorkspace();
     if (plan.global) {
         w.bbox = reinterpret_cast<int *>(p + off);
         off += up((size_t)num_clouds * 6 * 4);
-        w.keys_in = reinterpret_cast<unsigned long long *>(p + off);
-        off += up((size_t)rows * 8);
-        w.keys_out = reinterpret_cast<unsigned long long *>(p + off);
-        off += up((size_t)rows * 8);
-        w.vals_in = reinterpret_cast<unsigned int *>(p + off);
-        off += up((size_t)rows * 4);
-        w.vals_out = reinterpret_cast<unsigned int *>(p + off);
-        off += up((size_t)rows * 4);
-        w.sort_tmp = p + off;
-        w.sort_tmp_bytes = sort_pairs_tmp_bytes(rows);
-        off += up(w.sort_tmp_bytes + 256);
+        w.sort = carve_sort_workspace(p + off, rows, true, false);
+        off += w.sort.bytes;
     }
     w.bytes = off;
     return w;
@@ -791,19 +773,18 @@ int grid_build(const float *x, const int64_t *seg, int num_clouds, int64_t rows,
     hipLaunchKernelGGL(gridg_bbox_kernel, dim3(chunks, num_clouds), dim3(GG_BLOCK), 0, s, x, seg, N, w.bbox);
     hipLaunchKernelGGL(gridg_info_kernel, dim3((num_clouds + 63) / 64), dim3(64), 0, s, w.bbox, seg, N, num_clouds, cell,
                        target, G, w.info);
-    hipLaunchKernelGGL(gridg_key_kernel, dim3(chunks, num_clouds), dim3(GG_BLOCK), 0, s, x, seg, N, G, w.info, w.keys_in,
-                       w.vals_in);
+    hipLaunchKernelGGL(gridg_key_kernel, dim3(chunks, num_clouds), dim3(GG_BLOCK), 0, s, x, seg, N, G, w.info, w.sort.keys_in,
+                       w.sort.vals_in);
     if (int rc = check_launch()) return rc;
-    unsigned bits = 1;
-    const unsigned long long total = (unsigned long long)num_clouds * (unsigned long long)G * G * G;
-    while (bits < 63 && (1ull << bits) < total) ++bits;
-    if (int rc = sort_pairs_u64_u32(w.sort_tmp, w.sort_tmp_bytes, w.keys_in, w.keys_out, w.vals_in, w.vals_out, rows, bits, s))
+    const unsigned bits = sort_bits((unsigned __int128)num_clouds * (unsigned long long)G * G * G);
+    if (int rc = sort_pairs_u64_u32(w.sort.tmp, w.sort.tmp_bytes, w.sort.keys_in, w.sort.keys_out, w.sort.vals_in, w.sort.vals_out,
+                                    rows, bits, s))
         return rc;
     hipLaunchKernelGGL(gridg_fill_kernel, dim3((unsigned)((rows + GG_BLOCK - 1) / GG_BLOCK)), dim3(GG_BLOCK), 0, s, x, seg,
-                       N, G, rows, w.keys_out, w.vals_out, w.sorted_pt);
+                       N, G, rows, w.sort.keys_out, w.sort.vals_out, w.sorted_pt);
     const unsigned cchunks = (unsigned)(((size_t)G * G * G + 1 + GG_BLOCK - 1) / GG_BLOCK);
     hipLaunchKernelGGL(gridg_cellstart_kernel, dim3(cchunks, num_clouds), dim3(GG_BLOCK), 0, s, seg, N, G, w.info,
-                       w.keys_out, w.cell_start);
+                       w.sort.keys_out, w.cell_start);
     return check_launch();
 }
 

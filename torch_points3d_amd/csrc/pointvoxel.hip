@@ -14,7 +14,7 @@
 // A run of more than PV_LONG_RUN = 64 slots (a stride-16 voxel holds hundreds of points) is summed by one workgroup in
 // PV_PIECES = 16 contiguous pieces of ceil(n / 16) slots, added in piece order: the association depends on the run length
 // only -- reproducible, not the sequential sum bit for bit.  An index outside its row range counts as absent everywhere.
-#include "grid.h"
+#include "sorted_keys.h"
 
 namespace tp3d {
 
@@ -97,39 +97,7 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_invert_start_kernel(const unsigne
 {
     const int64_t v = (int64_t)blockIdx.x * PV_BLOCK + threadIdx.x;
     if (v > Nv) return;
-    int64_t lo = 0, hi = slots;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (sorted[mid] < (unsigned long long)v) lo = mid + 1;
-        else hi = mid;
-    }
-    start[v] = (int)lo;
-}
-
-struct PvInvertWorkspace {
-    unsigned long long *keys_in, *keys_out;
-    unsigned int *vals_in;
-    void *tmp;
-    size_t tmp_bytes, bytes;
-};
-
-static PvInvertWorkspace carve_pv_invert_workspace(void *ws, int64_t slots)
-{
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    PvInvertWorkspace w;
-    char *p = static_cast<char *>(ws);
-    size_t off = 0;
-    w.keys_in = reinterpret_cast<unsigned long long *>(p + off);
-    off += up((size_t)slots * 8);
-    w.keys_out = reinterpret_cast<unsigned long long *>(p + off);
-    off += up((size_t)slots * 8);
-    w.vals_in = reinterpret_cast<unsigned int *>(p + off);
-    off += up((size_t)slots * 4);
-    w.tmp = p + off;
-    w.tmp_bytes = sort_pairs_tmp_bytes(slots);
-    off += up(w.tmp_bytes + 256);
-    w.bytes = off;
-    return w;
+    start[v] = (int)lower_bound_u64(sorted, slots, (unsigned long long)v);
 }
 
 // ------------------------------------------------------------------------------------------------------ feature kernels
@@ -322,7 +290,7 @@ TP3D_EXPORT int tp3d_pv_trilinear_f32(const float *pc, int32_t *idx8, int64_t N,
 TP3D_EXPORT size_t tp3d_pv_invert_workspace_bytes(int64_t N, int K)
 {
     if (N <= 0 || K <= 0 || N >= 0x7fffffff / K) return 0;
-    return carve_pv_invert_workspace(nullptr, N * K).bytes;
+    return carve_sort_workspace(nullptr, N * K, false, false).bytes;
 }
 
 TP3D_EXPORT int tp3d_pv_invert_i32(const int32_t *table, int64_t N, int K, int64_t Nv, int32_t *start, int32_t *order,
@@ -334,15 +302,13 @@ TP3D_EXPORT int tp3d_pv_invert_i32(const int32_t *table, int64_t N, int K, int64
     const int64_t slots = N * K;
     if (slots == 0) return zero_async(start, (size_t)(Nv + 1) * sizeof(int32_t), s);
     if (!table || !order || !workspace) return TP3D_E_BADARG;
-    PvInvertWorkspace w = carve_pv_invert_workspace(workspace, slots);
+    SortWorkspace w = carve_sort_workspace(workspace, slots, false, false);  // the values are sorted into `order`
     if (workspace_bytes < w.bytes) return TP3D_E_BADARG;
     const unsigned blocks = (unsigned)((slots + PV_BLOCK - 1) / PV_BLOCK);
     hipLaunchKernelGGL(pv_invert_keys_kernel, dim3(blocks), dim3(PV_BLOCK), 0, s, table, slots, Nv, w.keys_in, w.vals_in);
     if (int rc = check_launch()) return rc;
-    unsigned bits = 1;  // the keys are 0 .. Nv
-    while (bits < 63 && (1ull << bits) <= (unsigned long long)Nv) ++bits;
     if (int rc = sort_pairs_u64_u32(w.tmp, w.tmp_bytes, w.keys_in, w.keys_out, w.vals_in, reinterpret_cast<unsigned int *>(order),
-                                    slots, bits, s))
+                                    slots, sort_bits((unsigned __int128)Nv + 1), s))  // the keys are 0 .. Nv
         return rc;
     hipLaunchKernelGGL(pv_invert_start_kernel, dim3((unsigned)((Nv + 1 + PV_BLOCK - 1) / PV_BLOCK)), dim3(PV_BLOCK), 0, s, w.keys_out,
                        slots, Nv, start);

@@ -12,15 +12,11 @@
 // the W[k] tile are staged in LDS, contracted with v_mfma_f32_16x16x4_f32, accumulators stay in registers across k;
 // nothing of size N*K*C is written to memory.  The gather also range-checks every index against the source row count.
 // No float atomics: forward, dX and dW are bit-reproducible.
-#include <cstring>
-
-#include <rocprim/rocprim.hpp>
-
-#include "grid.h"
+#include "sorted_keys.h"
 
 namespace tp3d {
 
-constexpr int SP_BLOCK = 256;
+constexpr int SP_BLOCK = SK_BLOCK;
 constexpr int SP_COORD_LIMIT = 1 << 18;  // |coord| below this at tensor stride 1
 constexpr int SP_BATCH_LIMIT = 1 << 9;   // batch below this
 constexpr int SP_META = 16;
@@ -41,19 +37,10 @@ __device__ __forceinline__ int sp_floor_to(int c, int m)
 // set may hold -2^18 itself, the floor of -(2^18 - 1), so the floor of an accepted voxel is accepted at the coarser stride.
 __device__ __forceinline__ bool sp_coord_ok(int c, int ts) { return c < SP_COORD_LIMIT && c > -SP_COORD_LIMIT - ts + 1; }
 
-__global__ void sp_meta_init_kernel(int *meta)
-{
-    const int t = threadIdx.x;
-    if (t < 3) meta[t] = 0x7fffffff;
-    else if (t < 7) meta[t] = (int)0x80000000;
-    else if (t < SP_META) meta[t] = 0;
-}
-
 // bounding box of the (floored) coordinates + the range flag
 __global__ __launch_bounds__(SP_BLOCK) void sp_bounds_kernel(const int *__restrict__ coords, int64_t N, int ts, int down,
                                                               int *__restrict__ meta)
 {
-    __shared__ int s_red[8][SP_BLOCK / 64];
     int v[8] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000, (int)0x80000000, 0};
     for (int64_t i = (int64_t)blockIdx.x * SP_BLOCK + threadIdx.x; i < N; i += (int64_t)gridDim.x * SP_BLOCK) {
 #pragma unroll
@@ -74,26 +61,7 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_bounds_kernel(const int *__restri
         }
         v[6] = max(v[6], b);
     }
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const int o = __shfl_xor(v[k], off);
-            v[k] = k < 3 ? min(v[k], o) : (k < 7 ? max(v[k], o) : (v[k] | o));
-        }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s_red[k][wave] = v[k];
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        const int k = threadIdx.x;
-        int r = s_red[k][0];
-        for (int w = 1; w < SP_BLOCK / 64; ++w) r = k < 3 ? min(r, s_red[k][w]) : (k < 7 ? max(r, s_red[k][w]) : (r | s_red[k][w]));
-        if (k < 3) atomicMin(&meta[k], r);
-        else if (k < 7) atomicMax(&meta[k], r);
-        else atomicOr(&meta[k], r);
-    }
+    box8_reduce_to(v, meta);
 }
 
 // key of (x, y, z, b) in the set described by meta; false when the voxel lies outside the set's bounding box
@@ -149,14 +117,6 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_input_finish_kernel(const unsigne
     if (i == 0) meta[8] = (int)N;
 }
 
-__global__ __launch_bounds__(SP_BLOCK) void sp_flag_kernel(const unsigned long long *__restrict__ keys, int64_t N,
-                                                            int *__restrict__ flags)
-{
-    const int64_t i = (int64_t)blockIdx.x * SP_BLOCK + threadIdx.x;
-    if (i >= N) return;
-    flags[i] = (i > 0 && keys[i] != keys[i - 1]) ? 1 : 0;
-}
-
 // stride-2 set: the first slot of every run of equal keys writes the voxel (keys ascend = (batch, x, y, z) order)
 __global__ __launch_bounds__(SP_BLOCK) void sp_compact_kernel(const unsigned long long *__restrict__ keys,
                                                                const unsigned int *__restrict__ vals,
@@ -202,12 +162,7 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_kmap_kernel(const int *__restrict
     unsigned long long key;
     int found = -1;
     if (sp_key(meta, qcoords[q * 4 + 0] + ox, qcoords[q * 4 + 1] + oy, qcoords[q * 4 + 2] + oz, qcoords[q * 4 + 3], &key)) {
-        int64_t lo = 0, hi = Ns;  // first slot with keys[slot] >= key
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (keys[mid] < key) lo = mid + 1;
-            else hi = mid;
-        }
+        const int64_t lo = lower_bound_u64(keys, Ns, key);
         if (lo < Ns && keys[lo] == key) {
             const int r = rows[lo];
             found = (r >= 0 && r < Ns) ? r : -1;
@@ -421,54 +376,6 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_wgrad_kernel(const float *__restr
     }
 }
 
-struct SparseWorkspace {
-    unsigned long long *keys_in, *keys_out;
-    unsigned int *vals_in, *vals_out;
-    int *flags, *cid;
-    void *tmp;
-    size_t tmp_bytes, bytes;
-};
-
-static size_t sparse_tmp_bytes(int64_t N)
-{
-    size_t sort_bytes = sort_pairs_tmp_bytes(N), scan_bytes = 0;
-    (void)rocprim::inclusive_scan(nullptr, scan_bytes, (const int *)nullptr, (int *)nullptr, (size_t)N, rocprim::plus<int>(),
-                                  (hipStream_t)0);
-    return sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-}
-
-static SparseWorkspace carve_sparse_workspace(void *ws, int64_t N)
-{
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    SparseWorkspace w;
-    char *p = static_cast<char *>(ws);
-    size_t off = 0;
-    w.keys_in = reinterpret_cast<unsigned long long *>(p + off);
-    off += up((size_t)N * 8);
-    w.keys_out = reinterpret_cast<unsigned long long *>(p + off);
-    off += up((size_t)N * 8);
-    w.vals_in = reinterpret_cast<unsigned int *>(p + off);
-    off += up((size_t)N * 4);
-    w.vals_out = reinterpret_cast<unsigned int *>(p + off);
-    off += up((size_t)N * 4);
-    w.flags = reinterpret_cast<int *>(p + off);
-    off += up((size_t)N * 4);
-    w.cid = reinterpret_cast<int *>(p + off);
-    off += up((size_t)N * 4);
-    w.tmp = p + off;
-    w.tmp_bytes = sparse_tmp_bytes(N);
-    off += up(w.tmp_bytes + 256);
-    w.bytes = off;
-    return w;
-}
-
-static int sp_hip_rc(hipError_t e)
-{
-    if (e == hipSuccess) return TP3D_OK;
-    set_last_hip_error(e);
-    return TP3D_E_LAUNCH;
-}
-
 // the sort covers the bits the key can have: the host knows the hard limits only (3 * 19 + 9 bits would pass 64, the
 // span flag rejects such a box), so 63
 constexpr unsigned SP_KEY_BITS = 63;
@@ -480,7 +387,7 @@ using namespace tp3d;
 TP3D_EXPORT size_t tp3d_sparse_workspace_bytes(int64_t N)
 {
     if (N <= 0 || N >= 0x7fffffff) return 0;
-    return carve_sparse_workspace(nullptr, N).bytes;
+    return carve_sort_workspace(nullptr, N, true, true).bytes;
 }
 
 TP3D_EXPORT int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int ts, int down, int64_t *keys_out,
@@ -490,11 +397,11 @@ TP3D_EXPORT int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int 
     if (N <= 0 || N >= 0x7fffffff || ts < 1 || ts >= SP_COORD_LIMIT || down < 0 || down >= SP_COORD_LIMIT || !coords || !keys_out || !rows_out || !meta ||
         !workspace || (down > 0 && !coords_out))
         return TP3D_E_BADARG;
-    SparseWorkspace w = carve_sparse_workspace(workspace, N);
+    SortWorkspace w = carve_sort_workspace(workspace, N, true, true);
     if (workspace_bytes < w.bytes) return TP3D_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
     const unsigned blocks = (unsigned)((N + SP_BLOCK - 1) / SP_BLOCK);
-    hipLaunchKernelGGL(sp_meta_init_kernel, dim3(1), dim3(64), 0, s, meta);
+    hipLaunchKernelGGL(box_init_kernel, dim3(1), dim3(64), 0, s, meta, SP_META);
     if (int rc = check_launch()) return rc;
     hipLaunchKernelGGL(sp_bounds_kernel, dim3(blocks > 1024 ? 1024 : blocks), dim3(SP_BLOCK), 0, s, coords, N, ts, down, meta);
     if (int rc = check_launch()) return rc;
@@ -507,11 +414,7 @@ TP3D_EXPORT int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int 
         hipLaunchKernelGGL(sp_input_finish_kernel, dim3(blocks), dim3(SP_BLOCK), 0, s, sorted, w.vals_out, N, rows_out, meta);
         return check_launch();
     }
-    hipLaunchKernelGGL(sp_flag_kernel, dim3(blocks), dim3(SP_BLOCK), 0, s, sorted, N, w.flags);
-    if (int rc = check_launch()) return rc;
-    size_t tb = w.tmp_bytes;
-    if (int rc = sp_hip_rc(rocprim::inclusive_scan(w.tmp, tb, (const int *)w.flags, w.cid, (size_t)N, rocprim::plus<int>(), s)))
-        return rc;
+    if (int rc = run_ids(sorted, N, w, s)) return rc;
     hipLaunchKernelGGL(sp_compact_kernel, dim3(blocks), dim3(SP_BLOCK), 0, s, sorted, w.vals_out, w.cid, coords, N, ts, down,
                        reinterpret_cast<unsigned long long *>(keys_out), rows_out, coords_out, meta);
     return check_launch();

@@ -13,16 +13,16 @@ constexpr int kWave = 64;
 
 void set_last_hip_error(hipError_t e);
 
-// Checks the launch that was just enqueued; called by every entry point.
-inline int check_launch()
+// HIP status -> library status; a failure is kept for tp3d_last_error.
+inline int hip_rc(hipError_t e)
 {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_hip_error(e);
-        return TP3D_E_LAUNCH;
-    }
-    return TP3D_OK;
+    if (e == hipSuccess) return TP3D_OK;
+    set_last_hip_error(e);
+    return TP3D_E_LAUNCH;
 }
+
+// Checks the launch that was just enqueued; called by every entry point.
+inline int check_launch() { return hip_rc(hipGetLastError()); }
 
 // Kernels that need more than 64 KiB of dynamic LDS must opt in once per (function, device).
 inline void allow_large_dynamic_lds(const void *func, int bytes, bool *done_per_device /*[64]*/)
@@ -38,13 +38,7 @@ inline void allow_large_dynamic_lds(const void *func, int bytes, bool *done_per_
 // Zero-fills a device buffer on the stream (used by the scatter-add backward entry points).
 inline int zero_async(void *ptr, size_t bytes, hipStream_t s)
 {
-    if (bytes == 0) return TP3D_OK;
-    hipError_t e = hipMemsetAsync(ptr, 0, bytes, s);
-    if (e != hipSuccess) {
-        set_last_hip_error(e);
-        return TP3D_E_LAUNCH;
-    }
-    return TP3D_OK;
+    return bytes == 0 ? TP3D_OK : hip_rc(hipMemsetAsync(ptr, 0, bytes, s));
 }
 
 // Squared distance in the one evaluation order shared with oracle/tpk_ref_cpu.c.

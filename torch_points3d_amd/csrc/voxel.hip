@@ -10,20 +10,16 @@
 //     mean mode: scatter_mean in ascending point order;  labels: one-hot scatter_add + argmax (ties -> lowest label)
 // Keys order lexicographically by (batch, z, y, x), so cluster ids are the ranks of the occupied voxels in that order.
 //
-// Device form: one stable LSD radix sort (rocPRIM) of (key, point index) over exactly the bits the key needs, boundary
-// flags + inclusive scan -> consecutive ids, one scatter pass.  Inside a cluster the sorted order IS ascending point
+// Device form (on the sorted-key core, sorted_keys.h): one stable radix sort of (key, point index) over exactly the bits
+// the key needs, run ids -> consecutive cluster ids, one scatter pass.  Inside a cluster the sorted order IS ascending point
 // index (stable sort of iota), which is what makes the fp32 means reproduce a sequential scatter_add bit for bit.
 // The host reads back 7 ints (bounding box of coords) before the sort and 1 int64 (cluster count) after it: the same
 // two device->host waits torch.unique costs the reference.
-#include <cstring>  // rocPRIM's texture iterator calls memset unqualified
-
-#include <rocprim/rocprim.hpp>
-
-#include "grid.h"
+#include "sorted_keys.h"
 
 namespace tp3d {
 
-constexpr int VX_BLOCK = 256;
+constexpr int VX_BLOCK = SK_BLOCK;
 constexpr int VX_COORD_LIMIT = 1 << 24;  // beyond this fp32 coordinates stop being exact integers (reference breaks too)
 
 __device__ __forceinline__ int voxel_coord(float p, float size)
@@ -32,20 +28,11 @@ __device__ __forceinline__ int voxel_coord(float p, float size)
     return (int)fminf(fmaxf(c, -(float)VX_COORD_LIMIT), (float)VX_COORD_LIMIT);
 }
 
-__global__ void voxel_bounds_init_kernel(int *bounds)
-{
-    const int t = threadIdx.x;
-    if (t < 3) bounds[t] = 0x7fffffff;
-    else if (t < 7) bounds[t] = (int)0x80000000;
-    else if (t == 7) bounds[t] = 0;
-}
-
 // bounds = [min x,y,z | max x,y,z | max batch | bad-input flag]
 __global__ __launch_bounds__(VX_BLOCK) void voxel_bounds_kernel(const float *__restrict__ pos,
                                                                  const int64_t *__restrict__ batch, int64_t N, float size,
                                                                  int *__restrict__ bounds)
 {
-    __shared__ int s_red[8][VX_BLOCK / 64];
     int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff};
     int mx[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
     int mb = (int)0x80000000, bad = 0;
@@ -64,25 +51,7 @@ __global__ __launch_bounds__(VX_BLOCK) void voxel_bounds_kernel(const float *__r
         }
     }
     int v[8] = {mn[0], mn[1], mn[2], mx[0], mx[1], mx[2], mb, bad};
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const int o = __shfl_xor(v[k], off);
-            v[k] = k < 3 ? min(v[k], o) : max(v[k], o);
-        }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s_red[k][wave] = v[k];
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        const int k = threadIdx.x;
-        int r = s_red[k][0];
-        for (int w = 1; w < VX_BLOCK / 64; ++w) r = k < 3 ? min(r, s_red[k][w]) : max(r, s_red[k][w]);
-        if (k < 3) atomicMin(&bounds[k], r);
-        else atomicMax(&bounds[k], r);
-    }
+    box8_reduce_to(v, bounds);
 }
 
 __global__ __launch_bounds__(VX_BLOCK) void voxel_key_kernel(const float *__restrict__ pos, const int64_t *__restrict__ batch,
@@ -99,14 +68,6 @@ __global__ __launch_bounds__(VX_BLOCK) void voxel_key_kernel(const float *__rest
     const int64_t b = batch ? batch[i] : 0;
     keys[i] = (unsigned long long)(((b * ez + cz) * ey + cy) * ex + cx);
     vals[i] = (unsigned int)i;
-}
-
-__global__ __launch_bounds__(VX_BLOCK) void voxel_flag_kernel(const unsigned long long *__restrict__ keys, int64_t N,
-                                                               int *__restrict__ flags)
-{
-    const int64_t i = (int64_t)blockIdx.x * VX_BLOCK + threadIdx.x;
-    if (i >= N) return;
-    flags[i] = (i > 0 && keys[i] != keys[i - 1]) ? 1 : 0;
 }
 
 // cid[i] = cluster of sorted slot i (inclusive scan of the boundary flags)
@@ -206,71 +167,6 @@ __global__ __launch_bounds__(VX_BLOCK) void cluster_majority_kernel(const int64_
     if (lane == 0) out[c] = best_lab + min_label;
 }
 
-struct VoxelWorkspace {
-    unsigned long long *keys_in, *keys_out;
-    unsigned int *vals_in, *vals_out;
-    int *flags, *cid;
-    void *tmp;
-    size_t tmp_bytes, bytes;
-};
-
-static int hip_rc(hipError_t e)
-{
-    if (e == hipSuccess) return TP3D_OK;
-    set_last_hip_error(e);
-    return TP3D_E_LAUNCH;
-}
-
-// The library's one radix-sort instantiation (also used by the sort-based grid build, grid.hip).
-size_t sort_pairs_tmp_bytes(int64_t n)
-{
-    size_t bytes = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, bytes, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                                    (const unsigned int *)nullptr, (unsigned int *)nullptr, (size_t)n, 0u, 64u,
-                                    (hipStream_t)0);
-    return bytes;
-}
-
-int sort_pairs_u64_u32(void *tmp, size_t tmp_bytes, const unsigned long long *keys_in, unsigned long long *keys_out,
-                       const unsigned int *vals_in, unsigned int *vals_out, int64_t n, unsigned bits, hipStream_t s)
-{
-    size_t tb = tmp_bytes;
-    return hip_rc(rocprim::radix_sort_pairs(tmp, tb, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, bits, s));
-}
-
-static size_t voxel_tmp_bytes(int64_t N)
-{
-    size_t sort_bytes = sort_pairs_tmp_bytes(N), scan_bytes = 0;
-    (void)rocprim::inclusive_scan(nullptr, scan_bytes, (const int *)nullptr, (int *)nullptr, (size_t)N,
-                                  rocprim::plus<int>(), (hipStream_t)0);
-    return sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-}
-
-static VoxelWorkspace carve_voxel_workspace(void *ws, int64_t N)
-{
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    VoxelWorkspace w;
-    char *p = static_cast<char *>(ws);
-    size_t off = 0;
-    w.keys_in = reinterpret_cast<unsigned long long *>(p + off);
-    off += up((size_t)N * 8);
-    w.keys_out = reinterpret_cast<unsigned long long *>(p + off);
-    off += up((size_t)N * 8);
-    w.vals_in = reinterpret_cast<unsigned int *>(p + off);
-    off += up((size_t)N * 4);
-    w.vals_out = reinterpret_cast<unsigned int *>(p + off);
-    off += up((size_t)N * 4);
-    w.flags = reinterpret_cast<int *>(p + off);
-    off += up((size_t)N * 4);
-    w.cid = reinterpret_cast<int *>(p + off);
-    off += up((size_t)N * 4);
-    w.tmp = p + off;
-    w.tmp_bytes = voxel_tmp_bytes(N);
-    off += up(w.tmp_bytes + 256);
-    w.bytes = off;
-    return w;
-}
-
 }  // namespace tp3d
 
 using namespace tp3d;
@@ -281,7 +177,7 @@ TP3D_EXPORT int tp3d_voxel_bounds_f32(const float *pos, const int64_t *batch, in
     if (N < 0 || N >= 0x7fffffff || !(size > 0.0f) || !bounds) return TP3D_E_BADARG;
     if (N > 0 && !pos) return TP3D_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(voxel_bounds_init_kernel, dim3(1), dim3(64), 0, s, bounds);
+    hipLaunchKernelGGL(box_init_kernel, dim3(1), dim3(64), 0, s, bounds, 8);
     if (int rc = check_launch()) return rc;
     if (N == 0) return TP3D_OK;
     int64_t blocks = (N + VX_BLOCK - 1) / VX_BLOCK;
@@ -293,7 +189,7 @@ TP3D_EXPORT int tp3d_voxel_bounds_f32(const float *pos, const int64_t *batch, in
 TP3D_EXPORT size_t tp3d_voxel_workspace_bytes(int64_t N)
 {
     if (N <= 0 || N >= 0x7fffffff) return 0;
-    return carve_voxel_workspace(nullptr, N).bytes;
+    return carve_sort_workspace(nullptr, N, true, true).bytes;
 }
 
 TP3D_EXPORT int tp3d_voxel_cluster_f32(const float *pos, const int64_t *batch, int64_t N, float size,
@@ -313,9 +209,8 @@ TP3D_EXPORT int tp3d_voxel_cluster_f32(const float *pos, const int64_t *batch, i
     // number of key bits: extents are < 2^26 each and nb <= 2^30, so use 128-bit products to detect overflow
     const unsigned __int128 total = (unsigned __int128)ex * (unsigned __int128)ey * (unsigned __int128)ez * (unsigned __int128)nb;
     if (total >> 63) return TP3D_E_TOOBIG;
-    unsigned bits = 1;
-    while (bits < 63 && ((unsigned __int128)1 << bits) < total) ++bits;
-    VoxelWorkspace w = carve_voxel_workspace(workspace, N);
+    const unsigned bits = sort_bits(total);
+    SortWorkspace w = carve_sort_workspace(workspace, N, true, true);
     if (workspace_bytes < w.bytes) return TP3D_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
     const unsigned blocks = (unsigned)((N + VX_BLOCK - 1) / VX_BLOCK);
@@ -324,11 +219,7 @@ TP3D_EXPORT int tp3d_voxel_cluster_f32(const float *pos, const int64_t *batch, i
     if (int rc = check_launch()) return rc;
     if (int rc = sort_pairs_u64_u32(w.tmp, w.tmp_bytes, w.keys_in, w.keys_out, w.vals_in, w.vals_out, N, bits, s))
         return rc;
-    hipLaunchKernelGGL(voxel_flag_kernel, dim3(blocks), dim3(VX_BLOCK), 0, s, w.keys_out, N, w.flags);
-    if (int rc = check_launch()) return rc;
-    size_t tb = w.tmp_bytes;
-    if (int rc = hip_rc(rocprim::inclusive_scan(w.tmp, tb, (const int *)w.flags, w.cid, (size_t)N, rocprim::plus<int>(), s)))
-        return rc;
+    if (int rc = run_ids(w.keys_out, N, w, s)) return rc;
     if (int rc = zero_async(meta, (size_t)(1 + nb) * sizeof(int64_t), s)) return rc;
     hipLaunchKernelGGL(voxel_scatter_kernel, dim3(blocks), dim3(VX_BLOCK), 0, s, w.vals_out, w.cid, N, cluster, order,
                        cluster_start, last, batch, nb, reinterpret_cast<unsigned long long *>(meta));

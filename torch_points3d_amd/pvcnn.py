@@ -62,16 +62,6 @@ def _quantize(pc, s):
     return q
 
 
-def _lookup(q, ksize, step, target):
-    """rows of the coordinate set `target` at q + offsets (tp3d_sparse_kmap_i32 takes any query coordinates)"""
-    dev = q.device
-    table = torch.empty((q.shape[0], ksize ** 3), dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        _lib.call("tp3d_sparse_kmap_i32", _lib.ptr(q), q.shape[0], ksize, int(step), 1, _lib.ptr(target.keys), _lib.ptr(target.rows),
-                  _lib.ptr(target.meta), target.n, _lib.ptr(table), _lib.stream_ptr(dev))
-    return table
-
-
 def _trilinear(pc, idx8, n_voxels, s, nearest):
     dev = pc.device
     w = torch.empty(idx8.shape, dtype=torch.float32, device=dev)
@@ -146,7 +136,7 @@ class _Devoxelize(torch.autograd.Function):
 
 def _voxelize_tables(z, q, target, s):
     """point -> voxel row table of stride s against the coordinate set `target`, its counts and inverted form, cached"""
-    idx = _lookup(q, 1, 1, target)
+    idx = sc._search(q, q.shape[0], 1, 1, 1, target)
     start, order = _invert(idx, target.n)
     counts = start[1:] - start[:-1]
     z.additional_features["idx_query"][s] = idx.view(-1)
@@ -193,7 +183,8 @@ def voxel_to_point(x, z, nearest=False):
         if target is None:
             raise RuntimeError("voxel_to_point: no coordinate set of tensor stride %d" % x.s)
         pc = z.C.float().contiguous()
-        idx8 = _lookup(_quantize(pc, x.s), 2, x.s, target)
+        q = _quantize(pc, x.s)
+        idx8 = sc._search(q, q.shape[0], 2, x.s, 1, target)
         weights = _trilinear(pc, idx8, target.n, x.s, nearest)
         z.idx_query[x.s] = idx8
         z.weights[x.s] = weights

@@ -98,17 +98,19 @@ class _KernelMap(object):
         self.forward, self.inverse, self.n_in, self.n_out, self.K = forward, inverse, n_in, n_out, K
 
 
-def _search(queries, ksize, step, sign, target):
-    dev = queries.coords.device
-    table = torch.empty((queries.n, ksize ** 3), dtype=torch.int32, device=dev)
+def _search(coords, n, ksize, step, sign, target):
+    """(n, ksize^3) int32: rows of the coordinate set `target` at coords + sign * offsets * step, -1 where absent (any
+    query coordinates: a set's own, or the quantised points of pvcnn.py)"""
+    dev = coords.device
+    table = torch.empty((n, ksize ** 3), dtype=torch.int32, device=dev)
     with _lib.on_device(dev):
-        _lib.call("tp3d_sparse_kmap_i32", _lib.ptr(queries.coords), queries.n, ksize, int(step), sign, _lib.ptr(target.keys),
+        _lib.call("tp3d_sparse_kmap_i32", _lib.ptr(coords), n, ksize, int(step), sign, _lib.ptr(target.keys),
                   _lib.ptr(target.rows), _lib.ptr(target.meta), target.n, _lib.ptr(table), _lib.stream_ptr(dev))
     return table
 
 
 def _build_kmap(in_set, out_set, ksize, ts, same_set):
-    forward = _search(out_set, ksize, ts, 1, in_set)
+    forward = _search(out_set.coords, out_set.n, ksize, ts, 1, in_set)
     if same_set and ksize % 2 == 1:
         dev = forward.device
         inverse = torch.empty_like(forward)
@@ -116,7 +118,7 @@ def _build_kmap(in_set, out_set, ksize, ts, same_set):
             _lib.call("tp3d_sparse_kmap_mirror_i32", _lib.ptr(forward), in_set.n, ksize ** 3, _lib.ptr(inverse),
                       _lib.stream_ptr(dev))
     else:
-        inverse = _search(in_set, ksize, ts, -1, out_set)
+        inverse = _search(in_set.coords, in_set.n, ksize, ts, -1, out_set)
     return _KernelMap(forward, inverse, in_set.n, out_set.n, ksize ** 3)
 
 
