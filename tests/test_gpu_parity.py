@@ -230,7 +230,7 @@ def test_three_nn_grid_path_is_exact(hip, oracle, case):
 
 def _assert_scatter_grad(got, want, flat_idx, nbins):
     """(B, C, nbins) scatter-add gradients: bit-identical to the oracle's sequential sum wherever a destination collects
-    at most 128 slots (GS_HUB_MIN of csrc/csr.hip); longer runs are summed in a fixed parallel order, i.e. to round-off."""
+    at most 128 slots (GS_HUB_MIN of csrc/run_sum.hip); longer runs are summed in a fixed parallel order, i.e. to round-off."""
     for b in range(got.shape[0]):
         runs = torch.bincount(flat_idx[b], minlength=nbins)
         short = runs <= 128

@@ -45,6 +45,11 @@ GridWorkspace carve_grid_workspace(void *ws, int num_clouds, int64_t rows, GridP
 int grid_build(const float *x, const int64_t *seg, int num_clouds, int64_t rows, int N, int Lmax, float cell, float target,
                GridPlan plan, const GridWorkspace &w, hipStream_t s);
 
+// Enqueue build + radius query (grid.hip); seg/batch_y null => dense layout.
+int grid_ball_query(const float *x, const float *y, const int64_t *seg, const int64_t *batch_y, int num_clouds,
+                    int64_t rows, int N, int np, int64_t total_q, int Lmax, float radius, int nsample, int sort,
+                    int64_t *idx, float *dist2, void *workspace, size_t workspace_bytes, bool reuse_grid, hipStream_t s);
+
 int grid_knn(const float *x, const float *y, const int64_t *seg, const int64_t *batch_y, int num_clouds, int64_t rows,
              int N, int np, int64_t total_q, int Lmax, int k, float cell, int64_t *idx, float *dist2, void *workspace,
              size_t workspace_bytes, hipStream_t s);

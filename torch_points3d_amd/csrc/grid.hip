@@ -12,6 +12,7 @@
 #include <cstdlib>
 
 #include "grid.h"
+#include "inverse_table.h"
 
 namespace tp3d {
 
@@ -48,35 +49,20 @@ __device__ __forceinline__ GridInfo make_grid_info(const float lo3[3], const flo
     return gi;
 }
 
-// Exclusive scan of a cell histogram in LDS by one GB_BLOCK workgroup (per-thread serial chunk + wave scan +
-// cross-wave): cnt[k] and cs_out[k] become base + the start of bin k; cs_out[nused] = L (or `last` when given; not
+// Exclusive scan of a cell histogram in LDS by one GB_BLOCK workgroup (block_scan_chunk): cnt[k] and cs_out[k] become base + the start of bin k; cs_out[nused] = L (or `last` when given; not
 // written when last < 0: a slab that is not the cloud's last one).  Ends without a barrier.
 __device__ __forceinline__ void grid_scan_cells(int *cnt, int *cs_out, int nused, int L, int *s_scan, int base = 0,
                                                 int last = 0)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per = (nused + GB_BLOCK - 1) / GB_BLOCK;
-    const int k0 = min(tid * per, nused), k1 = min(k0 + per, nused);
-    int sum = 0;
-    for (int k = k0; k < k1; ++k) sum += cnt[k];
-    int incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) s_scan[wave] = incl;
-    __syncthreads();
-    int run = base + incl - sum;
-#pragma unroll
-    for (int w = 0; w < GB_BLOCK / 64; ++w) run += (w < wave) ? s_scan[w] : 0;  // the waves in front
+    int k0, k1;
+    int run = base + block_scan_chunk<GB_BLOCK>(cnt, nused, s_scan, k0, k1);
     for (int k = k0; k < k1; ++k) {
         const int v = cnt[k];
         cnt[k] = run;
         cs_out[k] = run;  // start of bin k
         run += v;
     }
-    if (tid == 0 && last >= 0) cs_out[nused] = last ? last : L;
+    if (threadIdx.x == 0 && last >= 0) cs_out[nused] = last ? last : L;
 }
 
 // Bounding box of the PT points each thread holds -> GridInfo of the cloud in s_info / info[b] (ends with a barrier).
@@ -137,7 +123,7 @@ __global__ __launch_bounds__(GB_BLOCK) void grid_build_kernel(const float *__res
     const float *p = x + lo * 3;
     const int nbins = G * G * G;
     int *cnt = reinterpret_cast<int *>(smem);
-    unsigned short *ord = reinterpret_cast<unsigned short *>(smem + (((size_t)nbins * 4 + 15) & ~(size_t)15));
+    unsigned short *ord = reinterpret_cast<unsigned short *>(smem + align_up((size_t)nbins * 4, 16));
     int *cs_out = cell_start + (size_t)b * (nbins + 1);
 
     // ---- bounding box
@@ -468,13 +454,7 @@ __global__ __launch_bounds__(GQ_BLOCK) void grid_query_kernel(
             run[u] = tot;
             tot += __builtin_popcount(wv[u]);
         }
-        int incl = tot;  // inclusive scan of the lane totals (Hillis-Steele on the cross-lane network)
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int up = __shfl_up(incl, off);
-            if (lane >= off) incl += up;
-        }
-        const int base = incl - tot;
+        const int base = wave_inclusive_scan(tot) - tot;  // set bits in the lanes in front
         *reinterpret_cast<uint4 *>(&pre[lane * 8]) =
             make_uint4((unsigned)(base + run[0]) | ((unsigned)(base + run[1]) << 16), (unsigned)(base + run[2]) | ((unsigned)(base + run[3]) << 16),
                        (unsigned)(base + run[4]) | ((unsigned)(base + run[5]) << 16), (unsigned)(base + run[6]) | ((unsigned)(base + run[7]) << 16));
@@ -712,7 +692,7 @@ GridPlan grid_plan(int Lmax)
 
 GridWorkspace carve_grid_workspace(void *ws, int num_clouds, int64_t rows, GridPlan plan)
 {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    auto up = [](size_t v) { return align_up(v, 256); };
     const int G = plan.G;
     GridWorkspace w;
     char *p = static_cast<char *>(ws);
@@ -741,16 +721,13 @@ int grid_build(const float *x, const int64_t *seg, int num_clouds, int64_t rows,
     const int G = plan.G;
     if (G < 2 || num_clouds <= 0) return TP3D_E_TOOBIG;
     if (!plan.global) {
-        const size_t lds = (((size_t)G * G * G * 4 + 15) & ~(size_t)15) + (size_t)Lmax * 2;
-        static bool attr_set[64] = {false};
-        allow_large_dynamic_lds(reinterpret_cast<const void *>(&grid_build_kernel), (int)GRID_LDS_BUDGET, attr_set);
+        const size_t lds = align_up((size_t)G * G * G * 4, 16) + (size_t)Lmax * 2;
+        allow_large_dynamic_lds<&grid_build_kernel>((int)GRID_LDS_BUDGET);
         if (Lmax <= GB_BLOCK * 16) {
             const size_t lds_reg = (size_t)G * G * G * 4;
 #define TP3D_BUILD_REG(PT)                                                                                            \
     do {                                                                                                              \
-        static bool set_##PT[64] = {false};                                                                           \
-        allow_large_dynamic_lds(reinterpret_cast<const void *>(&grid_build_reg_kernel<PT>), (int)GRID_LDS_BUDGET,     \
-                                set_##PT);                                                                            \
+        allow_large_dynamic_lds<&grid_build_reg_kernel<PT>>((int)GRID_LDS_BUDGET);                                    \
         hipLaunchKernelGGL(grid_build_reg_kernel<PT>, dim3(num_clouds, 8), dim3(GB_BLOCK), lds_reg, s, x, seg, N, cell, \
                            target, G, w.info, w.cell_start, w.sorted_pt);                                             \
     } while (0)

@@ -5,7 +5,7 @@
 //
 // HBM-bound copy: one lane per (centroid, sample) slot loads its int64 index once and walks a chunk of
 // channels; the (B,C,np,ns) output is written in coalesced rows, the gathers hit an N-float feature row.
-#include "tp3d_common.h"
+#include "inverse_table.h"
 
 namespace tp3d {
 
@@ -73,8 +73,7 @@ __global__ __launch_bounds__(GL_BLOCK) void group_fwd_lds_kernel(const float *__
 template <int CC>
 static void launch_group_lds(const float *features, const int64_t *idx, int B, int C, int N, int L, float *out, hipStream_t s)
 {
-    static bool attr_set[64] = {false};
-    allow_large_dynamic_lds(reinterpret_cast<const void *>(&group_fwd_lds_kernel<CC>), GL_LDS_FLOATS * 4, attr_set);
+    allow_large_dynamic_lds<&group_fwd_lds_kernel<CC>>(GL_LDS_FLOATS * 4);
     hipLaunchKernelGGL(group_fwd_lds_kernel<CC>, dim3((C + CC - 1) / CC, B), dim3(GL_BLOCK), (size_t)CC * N * 4, s, features,
                        idx, C, N, L, out);
 }
@@ -109,7 +108,7 @@ TP3D_EXPORT int tp3d_group_fwd_f32(const float *features, const int64_t *idx, in
 }
 
 // backward: grad_features[b,c,k] = sum over the slots l with idx[b,l] == k of grad_out[b,c,l], ascending l
-// (csr.hip: transpose the table once, then one gather-sum per destination -- no atomics, reproducible).
+// (inverse_table.hip: transpose the table once, then one gather-sum per destination -- no atomics, reproducible).
 TP3D_EXPORT int tp3d_group_bwd_f32(const float *grad_out, const int64_t *idx, int B, int C, int N, int np, int ns,
                                    float *grad_features, void *workspace, size_t workspace_bytes, void *stream)
 {

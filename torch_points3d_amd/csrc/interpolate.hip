@@ -5,8 +5,8 @@
 //
 // HBM-bound, write-dominated: one lane per unknown point i loads its 3 (idx, weight) pairs once and
 // walks a chunk of channels, so the (B,C,n) output is written in full coalesced rows while the gathers
-// hit a (m-float) feature row that stays in L1/L2.  Backward: csr.hip (transpose + gather-sum, no atomics).
-#include "tp3d_common.h"
+// hit a (m-float) feature row that stays in L1/L2.  Backward: inverse_table.hip + run_sum.hip (transpose + gather-sum, no atomics).
+#include "inverse_table.h"
 
 namespace tp3d {
 
@@ -100,9 +100,7 @@ template <int CC>
 static void launch_interp_lds(const float *features, const int64_t *idx, const float *weight, int B, int C, int m, int n,
                               float *out, hipStream_t s)
 {
-    static bool attr_set[64] = {false};
-    allow_large_dynamic_lds(reinterpret_cast<const void *>(&three_interpolate_fwd_lds_kernel<CC>), TL_LDS_FLOATS * 4,
-                            attr_set);
+    allow_large_dynamic_lds<&three_interpolate_fwd_lds_kernel<CC>>(TL_LDS_FLOATS * 4);
     hipLaunchKernelGGL(three_interpolate_fwd_lds_kernel<CC>, dim3((C + CC - 1) / CC, B), dim3(TL_BLOCK), (size_t)CC * m * 4, s,
                        features, idx, weight, C, m, n, out);
 }
@@ -139,7 +137,7 @@ TP3D_EXPORT int tp3d_three_interpolate_fwd_f32(const float *features, const int6
 }
 
 // backward: grad_features[b,c,k] = sum over the slots (i,t) with idx[b,i,t] == k of w[b,i,t]*grad_out[b,c,i],
-// ascending (i,t) (csr.hip: transpose the (B, 3n) table once, then one weighted gather-sum per destination).
+// ascending (i,t) (inverse_table.hip: transpose the (B, 3n) table once, then one weighted gather-sum per destination).
 TP3D_EXPORT int tp3d_three_interpolate_bwd_f32(const float *grad_out, const int64_t *idx, const float *weight,
                                                int B, int C, int m, int n, float *grad_features, void *workspace,
                                                size_t workspace_bytes, void *stream)

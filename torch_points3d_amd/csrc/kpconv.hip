@@ -8,7 +8,8 @@
 // query: the KP x Mn influence weights live in LDS, neighbour feature rows are read as coalesced row segments
 // and KP accumulators per lane stay in registers, so HBM sees the neighbour rows once and wf once.
 // The per-query pieces shared with the deformable convolution are in kp_common.h; the inverted neighbour table of the
-// backward pass is nbr_table.hip.
+// backward pass is inverse_table.hip, the sum through it run_sum.hip.
+#include "inverse_table.h"
 #include "kp_common.h"
 
 namespace tp3d {
@@ -195,7 +196,7 @@ TP3D_EXPORT int tp3d_kpconv_weighted_f32(const float *query, const float *suppor
 //   d_x[m, :] = sum over slots (q, n) with nbr[q,n] == m of  sum_k h(|(s_m - q) - K_k|) * d_wf[q, k, :]
 // (reference: autograd through convolution_ops.py:92-98).  No float atomics: one wave per query writes the gradient row of
 // each of its slots, then one wave per support point sums the rows of the slots that reference it through the inverted
-// neighbour table (nbr_table.hip), in ascending slot order.
+// neighbour table (inverse_table.hip, run_sum.hip), in ascending slot order.
 namespace tp3d {
 
 // Backward, step 1 (one wave per query): per-slot gradient rows

@@ -16,6 +16,7 @@
 // d_wf on the matrix pipe (channels are the contraction index) to get the (kernel point, neighbour) sensitivities
 // the offset and modulation gradients are made of.  No atomics; every sum has a fixed order.
 // The per-query pieces shared with the rigid convolution are in kp_common.h.
+#include "inverse_table.h"
 #include "kp_common.h"
 
 namespace tp3d {

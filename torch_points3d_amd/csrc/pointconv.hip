@@ -49,12 +49,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_kernel(int64_t *__restrict__ 
             sum += a[k];
             a[k] = sum;  // inclusive inside the thread
         }
-        int64_t inc = sum;  // inclusive scan of the thread sums inside the wave
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-            const int64_t o = __shfl_up(inc, off);
-            if (lane >= off) inc += o;
-        }
+        const int64_t inc = wave_inclusive_scan(sum);  // of the thread sums inside the wave
         if (lane == kWave - 1) s_wave[wave] = inc;
         __syncthreads();
         int64_t before = s_carry;

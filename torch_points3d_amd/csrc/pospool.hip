@@ -13,11 +13,11 @@
 // lanes (a sine channel and its cosine channel in one lane: one sincosf for both) and the neighbour slots in a loop, so
 // HBM sees the neighbour rows once and (Nq, C) once.
 //
-// The backward pass (features only) sums per support point through the inverted neighbour table (nbr_table.hip): no
+// The backward pass (features only) sums per support point through the inverted neighbour table (inverse_table.hip): no
 // atomics, ascending slot order, the prior recomputed from the two positions.
 #include <algorithm>
 
-#include "tp3d_common.h"
+#include "inverse_table.h"
 
 namespace tp3d {
 

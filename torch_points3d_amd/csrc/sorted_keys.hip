@@ -32,7 +32,7 @@ unsigned sort_bits(unsigned __int128 total)
 
 SortWorkspace carve_sort_workspace(void *ws, int64_t n, bool with_vals_out, bool with_run_ids)
 {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    auto up = [](size_t v) { return align_up(v, 256); };
     char *p = static_cast<char *>(ws);
     size_t off = 0;
     auto take = [&](size_t bytes) {

@@ -212,12 +212,7 @@ __global__ __launch_bounds__(NG_BLOCK) void three_nn_grid_kernel(const float *__
         const int k0 = min(lane * per, ncells), k1 = min(k0 + per, ncells);
         int sum = 0;
         for (int k = k0; k < k1; ++k) sum += scur[k];
-        int incl = sum;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(incl, off);
-            if (lane >= off) incl += v;
-        }
+        const int incl = wave_inclusive_scan(sum);
         int run = incl - sum;
         for (int k = k0; k < k1; ++k) {
             const int v = scur[k];
@@ -325,9 +320,7 @@ TP3D_EXPORT int tp3d_three_nn_f32(const float *unknown, const float *known, int 
     if ((int64_t)n * 3 > INT32_MAX || (int64_t)m * 3 > INT32_MAX || B > 65535) return TP3D_E_TOOBIG;
     if (m >= NG_MIN_KNOWN && m <= NG_MAX_KNOWN && n >= 4 * m && n >= 1024) {
         // enough unknown points per known one to pay for binning the known cloud in every workgroup
-        static bool attr_set[64] = {false};
-        allow_large_dynamic_lds(reinterpret_cast<const void *>(&three_nn_grid_kernel), (int)nng_lds_bytes(NG_MAX_KNOWN),
-                                attr_set);
+        allow_large_dynamic_lds<&three_nn_grid_kernel>((int)nng_lds_bytes(NG_MAX_KNOWN));
         dim3 grid((n + NG_BLOCK * NG_QPT - 1) / (NG_BLOCK * NG_QPT), B);
         hipLaunchKernelGGL(three_nn_grid_kernel, grid, dim3(NG_BLOCK), nng_lds_bytes(m), (hipStream_t)stream, unknown,
                            known, n, m, dist, idx);

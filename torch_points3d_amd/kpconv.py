@@ -4,7 +4,7 @@ Mirrors `KPConv_ops` (torch_points3d/modules/KPConv/convolution_ops.py:19-107) a
 (modules/KPConv/kernels.py:20-104): same arguments, same shadow-neighbour convention (-1 -> zero feature), same
 influence / aggregation modes, same parameter names (`K_points`, `weight`).  Stage 1 (kernel-point weighted
 neighbourhood features) and its backward are HIP kernels (csrc/kpconv.hip; the inverted neighbour table the backward
-sums through is csrc/nbr_table.hip); stage 2 is the single
+sums through is csrc/inverse_table.hip, the sum itself csrc/run_sum.hip); stage 2 is the single
 (Nq, KP*Cin) x (KP*Cin, Cout) GEMM the reference's permute/matmul/sum amounts to; the kernel-weight gradient runs
 on the split-K MFMA kernel (csrc/gemm_tn.hip).  Differentiable wrt `features` and `K_values` (what the reference
 trains); positions and kernel points carry no gradient (kernels.py:57-59 sets requires_grad=False on K_points).

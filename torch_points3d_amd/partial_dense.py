@@ -8,7 +8,7 @@ Mirrors (same constructor arguments, attribute names -- hence state_dict keys --
   * `KNNNeighbourFinder`   torch_points3d/core/spatial_ops/neighbour_finder.py:42-47
 The reference gets the neighbour search from torch_cluster (`knn`) and the weighted sum from torch_scatter; here both
 are entry points of libtp3d_hip.so (csrc/knn.hip), and the backward scatter is the atomic-free inverse-index gather
-(csrc/csr.hip) shared with the dense path.
+(csrc/inverse_table.hip, csrc/run_sum.hip) shared with the dense path.
 """
 import torch
 import torch.nn as nn

@@ -8,7 +8,7 @@ radius 2.5 * sigma * prev_grid_size, bottleneck_ratio 2, `unary_2` and `shortcut
 
 The aggregation itself -- a parameter-free gather that multiplies every neighbour's feature row by a geometric prior of
 its relative position and reduces over the neighbours -- is one HIP kernel per direction (csrc/pospool.hip); the
-backward pass sums per support point through the inverted neighbour table shared with the KPConv kernels (no atomics).
+backward pass sums per support point through the inverted neighbour table shared with the KPConv kernels (csrc/inverse_table.hip; no atomics).
 Differentiable wrt `features`; positions carry no gradient.  Everything around it is shared with kpconv_blocks.py: the
 radius search, `GridSampling3D`, the strided shortcut (`fused.nbr_maxpool`), `fused.bn_act` / `fused.rows_seq` behind
 the same `fused=` switch and the `precomputed=` path.
