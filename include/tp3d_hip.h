@@ -640,6 +640,27 @@ int tp3d_pv_gather_f32(const float *src, const int32_t *table, const float *w, c
 int tp3d_pv_runsum_f32(const float *src, const int32_t *start, const int32_t *order, const float *w, const float *scale,
                        int64_t Nv, int K, int64_t Nsrc, int C, float *out, void *stream);
 
+/* Region growing of PointGroup (csrc/region_grow.hip)            [models/panoptic/pointgroup.py:98-121, region_grow]
+ *   The connected components of the graph that joins points i, j when labels[i] == labels[j], batch[i] == batch[j], the
+ *   label is not one of ignore[0 .. n_ignore) and (dx*dx + dy*dy) + dz*dz < radius * radius in fp32 -- the membership
+ *   test of tp3d_ball_query_partial_dense_f32, uncapped.  pos (N,3), labels (N), batch (N, ascending); ignore is DEVICE
+ *   memory.  Components of at least min_cluster_size points are written as a CSR, ordered by (label ascending, lowest
+ *   member ascending), members in ascending point index:
+ *     members (N; [0, M) valid) point indices;  member_cluster (N; [0, M) valid) cluster of each member slot;
+ *     starts (N + 1; [0, K] valid) slot range of each cluster;  cluster_label, cluster_cloud (N; [0, K) valid);
+ *     stats (8 int32): [0] largest neighbour count of a point (itself and duplicates included: the row length an
+ *     uncapped ball query would have), [1] K, [2] M, [3] flags: 1 a kept label outside [0, 4094], 2 a cloud id outside
+ *     [0, 1023], 4 a coordinate beyond +-2^24 cells, 8 more than 16382 cells of 1.01 * radius along an axis.  A point
+ *     that raises a flag is left out of every cluster (nothing wraps; a coordinate beyond the limit also stays out of
+ *     the cell box); the caller reads stats back once and decides.
+ *   The result does not depend on the execution order (min-root union-find: a component's root is its lowest index);
+ *   no float atomics.  Memory proportional to N: workspace tp3d_region_grow_workspace_bytes(N) (0: N not served). */
+size_t tp3d_region_grow_workspace_bytes(int64_t N);
+int tp3d_region_grow_f32(const float *pos, const int64_t *labels, const int64_t *batch, int64_t N, const int64_t *ignore,
+                         int n_ignore, float radius, int64_t min_cluster_size, int64_t *members, int64_t *member_cluster,
+                         int64_t *starts, int64_t *cluster_label, int64_t *cluster_cloud, int32_t *stats, void *workspace,
+                         size_t workspace_bytes, void *stream);
+
 /* =====================================================================================================
  * Launch plans (host arithmetic only, no device work): what an entry point WILL do for given sizes -- how it
  * splits the rows, how many partial rows it writes, how it carves its workspace.  tests/test_plans_cpu.py sweeps

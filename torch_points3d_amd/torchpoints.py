@@ -19,7 +19,7 @@ from . import _lib
 
 __all__ = ["furthest_point_sample", "ball_query", "three_nn", "three_interpolate", "grouping_operation"]
 # (message-passing side: fps_quota, fps_ragged, radius_edges, pointconv_rows, segment_max, rsconv_relation_rows,
-# rsconv_msgmax -- further down)
+# rsconv_msgmax; PointGroup's clustering: ClusterSet, region_grow_csr -- further down)
 
 
 def _dev(*tensors):
@@ -614,3 +614,151 @@ class _Grouping(torch.autograd.Function):
 def grouping_operation(features, idx):
     """features (B,C,N), idx (B,np,ns) -> (B,C,np,ns); differentiable wrt features."""
     return _Grouping.apply(features, idx)
+
+
+def segment_mean(rows, seg, index):
+    """out (S, C) = mean of rows[index[seg[s] : seg[s + 1]]] per segment s, summed in slot order (csrc/pointvoxel.hip's
+    run sums: no float atomics, reproducible); rows (R, C), seg (S + 1,) ascending from 0, index (E,) rows of `rows`.
+    An empty segment gives zeros.  Not differentiable (PointGroup's semantic certainty is computed without gradient)."""
+    dev = _dev(rows, seg, index)
+    if rows.dim() != 2 or seg.dim() != 1 or seg.numel() < 1 or index.dim() != 1:
+        raise ValueError("rows must be (R, C), seg (S + 1,) and index (E,)")
+    rows = _f32(rows)
+    S = seg.numel() - 1
+    out = torch.empty((S, rows.shape[1]), dtype=torch.float32, device=dev)
+    if S == 0:
+        return out
+    start, order = seg.int().contiguous(), index.int().contiguous()
+    scale = (1.0 / (seg[1:] - seg[:-1]).clamp(min=1).float()).contiguous()
+    with _lib.on_device(dev):
+        _lib.call("tp3d_pv_runsum_f32", _lib.ptr(rows), _lib.ptr(start), _lib.ptr(order), None, _lib.ptr(scale), S, 1,
+                  rows.shape[0], rows.shape[1], _lib.ptr(out), _lib.stream_ptr(dev))
+    return out
+
+
+class ClusterSet(object):
+    """Clusters of points as a CSR: cluster c owns members[starts[c] : starts[c + 1]] (point indices, ascending).
+
+    members, member_cluster (M,) int64; starts (K + 1,) int64; label, cloud (K,) int64 (the semantic label and the cloud
+    of each cluster); route: "device" when the HIP region growing produced the set, "host" when the reference's capped
+    walk had to (see region_grow_csr), "mixed" for a concatenation (`cat`) of sets of both kinds, None for a set built
+    from a list."""
+
+    __slots__ = ("members", "starts", "member_cluster", "label", "cloud", "route")
+
+    def __init__(self, members, starts, member_cluster=None, label=None, cloud=None, route=None):
+        self.members, self.starts, self.route = members, starts, route
+        K = starts.numel() - 1
+        if member_cluster is None:
+            member_cluster = torch.repeat_interleave(torch.arange(K, device=members.device), starts[1:] - starts[:-1])
+        self.member_cluster = member_cluster
+        self.label = label if label is not None else torch.full((K,), -1, dtype=torch.int64, device=members.device)
+        self.cloud = cloud if cloud is not None else torch.full((K,), -1, dtype=torch.int64, device=members.device)
+
+    def __len__(self):
+        return self.starts.numel() - 1
+
+    def sizes(self):
+        return self.starts[1:] - self.starts[:-1]
+
+    def to_list(self):
+        """the reference's form: one LongTensor of point indices per cluster -- views into `members`, no copies (one
+        host read of `starts`)"""
+        s = self.starts.tolist()
+        return [self.members[s[c]:s[c + 1]] for c in range(len(s) - 1)]
+
+    @classmethod
+    def from_list(cls, clusters, device=None, labels=None, batch=None, route=None):
+        """packs a list of index tensors (members are kept in the order given); labels / batch (N,), when given, fill
+        `label` / `cloud` from each cluster's first member"""
+        if device is None:
+            device = clusters[0].device if len(clusters) else torch.device("cpu")
+        sizes = torch.tensor([int(c.numel()) for c in clusters], dtype=torch.int64)
+        starts = torch.zeros(len(clusters) + 1, dtype=torch.int64)
+        starts[1:] = torch.cumsum(sizes, 0)
+        members = (torch.cat([c.reshape(-1).to(device).long() for c in clusters]) if len(clusters)
+                   else torch.zeros(0, dtype=torch.int64, device=device))
+        starts = starts.to(device)
+        label = cloud = None
+        if len(clusters) and members.numel() == int(starts[-1]) and int(sizes.min()) > 0:
+            first = members[starts[:-1]]
+            label = labels.to(device).long()[first] if labels is not None else None
+            cloud = batch.to(device).long()[first] if batch is not None else None
+        return cls(members, starts, None, label, cloud, route)
+
+    @classmethod
+    def cat(cls, sets):
+        """one set holding the clusters of `sets` one after the other"""
+        starts, off = [sets[0].starts[:1]], 0
+        member_cluster, k = [], 0
+        for s in sets:
+            starts.append(s.starts[1:] + off)
+            member_cluster.append(s.member_cluster + k)
+            off += s.members.numel()
+            k += len(s)
+        routes = set(s.route for s in sets)
+        return cls(torch.cat([s.members for s in sets]), torch.cat(starts), torch.cat(member_cluster),
+                   torch.cat([s.label for s in sets]), torch.cat([s.cloud for s in sets]),
+                   routes.pop() if len(routes) == 1 else "mixed")
+
+
+REGION_GROW_FLAGS = {1: "a label outside [0, 4094]", 2: "a cloud id outside [0, 1023]", 4: "a coordinate beyond 2^24 cells",
+                     8: "more than 16382 cells along an axis"}
+
+
+def region_grow_csr(pos, labels, batch, ignore_labels=(), radius=0.03, nsample=300, min_cluster_size=10, cap="reference"):
+    """PointGroup's clustering on the device: for every label that is not ignored, the sets of points of one cloud that
+    are connected through radius neighbourhoods, as a ClusterSet ordered by (label, lowest member), members ascending.
+
+    pos (N,3), labels (N,), batch (N,) sorted: device tensors (there is no CPU fallback); ignore_labels a list or tensor.
+    One HIP call (csrc/region_grow.hip) and one device-to-host read of 8 ints.
+
+    cap="reference" (default): the reference keeps only the first `nsample` neighbours of a point.  When no point has
+    more than `nsample` neighbours (itself and duplicates counted) the device result IS the reference's and
+    route == "device".  Otherwise the reference's walk runs over a truncated, directed table and its result depends on
+    the visiting order, which no parallel pass reproduces: the call then takes the capped path (device ball-query
+    table, walk on the host) and packs its clusters into the same form, route == "host".  An input the kernel's key does
+    not hold (see REGION_GROW_FLAGS) goes the same way.  The overflow is only known once the device pass has run, so a
+    "host" call costs that pass AND the whole capped path.
+
+    cap=None: always the device result -- uncapped connected components, as in the PointGroup paper.  This is NOT what
+    the reference computes when a neighbourhood overflows `nsample`: there the reference may split a component or drop
+    points, here it never does.  A flagged input raises."""
+    if cap not in ("reference", None):
+        raise ValueError('cap must be "reference" or None')
+    if pos.dim() != 2 or pos.shape[1] != 3 or labels.dim() != 1 or not (pos.shape[0] == labels.shape[0] == batch.shape[0]):
+        raise ValueError("region_grow_csr expects pos (N,3), labels (N,), batch (N,)")
+    dev = _dev(pos, labels, batch)
+    N = pos.shape[0]
+    if torch.is_tensor(ignore_labels):
+        ignore = ignore_labels.to(dev).long().reshape(-1).contiguous()
+    else:
+        ignore = torch.tensor([int(v) for v in ignore_labels], dtype=torch.int64, device=dev)
+    if N == 0:
+        z = torch.zeros(0, dtype=torch.int64, device=dev)
+        return ClusterSet(z, torch.zeros(1, dtype=torch.int64, device=dev), z, z, z, "device")
+    x, lab, bat = _f32(pos), _i64(labels), _i64(batch)
+    nbytes = _lib.load().tp3d_region_grow_workspace_bytes(N)
+    if nbytes == 0:
+        raise ValueError("region_grow_csr: %d points are more than the kernels index" % N)
+    ws = _lib.workspace("region_grow", nbytes, dev)
+    members = torch.empty(N, dtype=torch.int64, device=dev)
+    member_cluster = torch.empty(N, dtype=torch.int64, device=dev)
+    starts = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    label = torch.empty(N, dtype=torch.int64, device=dev)
+    cloud = torch.empty(N, dtype=torch.int64, device=dev)
+    stats = torch.empty(8, dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_region_grow_f32", _lib.ptr(x), _lib.ptr(lab), _lib.ptr(bat), N, _lib.ptr(ignore), ignore.numel(),
+                  float(radius), int(min_cluster_size), _lib.ptr(members), _lib.ptr(member_cluster), _lib.ptr(starts),
+                  _lib.ptr(label), _lib.ptr(cloud), _lib.ptr(stats), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+    most, K, M, flags = stats.tolist()[:4]  # the call's only device-to-host transfer
+    if cap is None:
+        if flags:
+            raise ValueError("region_grow_csr: " + ", ".join(t for b, t in REGION_GROW_FLAGS.items() if flags & b))
+    elif flags or most > int(nsample):
+        from torch_points_kernels import region_grow as capped  # (imports this module: resolved at call time)
+        found = capped(pos, labels, batch, ignore_labels=ignore, radius=radius, nsample=nsample,
+                       min_cluster_size=min_cluster_size)
+        return ClusterSet.from_list([torch.sort(c)[0] for c in found], device=dev, labels=lab, batch=bat, route="host")
+    return ClusterSet(members[:M], starts[:K + 1], member_cluster[:M], label[:K], cloud[:K], "device")
