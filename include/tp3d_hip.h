@@ -661,6 +661,33 @@ int tp3d_region_grow_f32(const float *pos, const int64_t *labels, const int64_t 
                          int64_t *starts, int64_t *cluster_label, int64_t *cluster_cloud, int32_t *stats, void *workspace,
                          size_t workspace_bytes, void *stream);
 
+/* Registration descriptors (csrc/registration.hip)   [core/losses/metric_losses.py, utils/registration.py, geometry.py]
+ *   tp3d_feature_nn_f32: a (P, C), b (S, C) fp32 -> dist2 (P) fp32, idx (P) int64: dist2[i] = min over the allowed j of
+ *     sum_c (a[i][c] - b[j][c])^2, idx[i] the LOWEST such j among exact ties.  The difference form in fp32: per tile of
+ *     32 / 64 / 128 channels (the least that holds C; 64 for C > 128, tiles added in ascending order) four fma chains over
+ *     c = k, k + 4, ... ascending, combined as (s0 + s1) + (s2 + s3).  pos_a (P, 3) and pos_b (S, 3), both or neither:
+ *     j is allowed only if sqrt(((dx*dx + dy*dy) + dz*dz) + 1e-7) > min_dist in fp32 (pdist(..., "L2") > min_dist).  A row
+ *     without an allowed candidate (S == 0 included) gets idx = -1, dist2 = +inf; a NaN distance never wins.  S is split
+ *     over workgroups and the per-split minima of (distance bits << 32 | j) are combined by an integer minimum: no float
+ *     atomics, repeats are bit-equal.  workspace: tp3d_feature_nn_workspace_bytes(P, S, C) (0: nothing to do or too big).
+ *   Fast Global Registration, one iteration = tp3d_fgr_accumulate_f32 + tp3d_fgr_solve with the same N, iter, workspace
+ *     (tp3d_fgr_workspace_bytes(N): the pose T_res and mu in double, then the per-block partial sums), iter = 0, 1, ... in
+ *     order.  accumulate: s = R p + t with the pose of the workspace (identity at iter 0), the Geman-McClure weight
+ *     w = mu / (mu + |q - s|^2) (1 at iter 0), and the 21 + 6 distinct entries of A^T A and A^T b of get_matrix_system
+ *     (rows w [-[s]x | I], right side w (q - s)) summed in double per block.  solve (one wave): the partials added in
+ *     block order, the 6 x 6 system by Gaussian elimination with partial pivoting in double, T = the Rodrigues matrix of
+ *     get_trans (identity rotation at theta == 0), T_res <- T T_res, mu <- mu_init at iter 0 and mu / 2 when iter > 0 and
+ *     iter % 5 == 0 (it weighs the NEXT iteration, as in the reference); T (16 floats, row-major) receives T_res.  A pivot
+ *     that is exactly 0, or a solution that is not finite, leaves T_res as it was (the reference raises).  The host reads
+ *     nothing between the launches. */
+size_t tp3d_feature_nn_workspace_bytes(int64_t P, int64_t S, int C);
+int tp3d_feature_nn_f32(const float *a, const float *b, const float *pos_a, const float *pos_b, int64_t P, int64_t S, int C,
+                        float min_dist, float *dist2, int64_t *idx, void *workspace, size_t workspace_bytes, void *stream);
+size_t tp3d_fgr_workspace_bytes(int64_t N);
+int tp3d_fgr_accumulate_f32(const float *xyz, const float *xyz_target, int64_t N, int iter, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int tp3d_fgr_solve(int64_t N, int iter, double mu_init, float *T, void *workspace, size_t workspace_bytes, void *stream);
+
 /* =====================================================================================================
  * Launch plans (host arithmetic only, no device work): what an entry point WILL do for given sizes -- how it
  * splits the rows, how many partial rows it writes, how it carves its workspace.  tests/test_plans_cpu.py sweeps

@@ -93,6 +93,9 @@ SIGNATURES = {
     "tp3d_pv_gather_f32": [_p, _p, _p, _p, _l, _i, _l, _i, _p, _p],
     "tp3d_pv_runsum_f32": [_p, _p, _p, _p, _p, _l, _i, _l, _i, _p, _p],
     "tp3d_region_grow_f32": [_p, _p, _p, _l, _p, _i, _f, _l, _p, _p, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
+    "tp3d_feature_nn_f32": [_p, _p, _p, _p, _l, _l, _i, _f, _p, _p, _p, ctypes.c_size_t, _p],
+    "tp3d_fgr_accumulate_f32": [_p, _p, _l, _i, _p, ctypes.c_size_t, _p],
+    "tp3d_fgr_solve": [_l, _i, ctypes.c_double, _p, _p, ctypes.c_size_t, _p],
     # launch plans (host arithmetic; the last argument is a HOST int64 array)
     "tp3d_gemm_tn_plan": [_l, _i, _i, _p],
     "tp3d_gemm_tn_x3_plan": [_l, _i, _i, _p],
@@ -131,6 +134,8 @@ MISC = {
     "tp3d_sparse_wgrad_workspace_floats": (_z, [_l, _i, _i, _i]),
     "tp3d_pv_invert_workspace_bytes": (_z, [_l, _i]),
     "tp3d_region_grow_workspace_bytes": (_z, [_l]),
+    "tp3d_feature_nn_workspace_bytes": (_z, [_l, _l, _i]),
+    "tp3d_fgr_workspace_bytes": (_z, [_l]),
 }
 ABI_VERSION = 39
 

@@ -1,0 +1,307 @@
+"""Registration descriptors (reference torch_points3d/models/registration/{base,kpconv,spconv3d}.py,
+core/losses/metric_losses.py, utils/registration.py, metrics/registration_metrics.py, metrics/registration_tracker.py) on the
+device: fragment descriptors trained with a mined contrastive loss, evaluated by feature matching and a robust pose solve.
+
+  pdist                            the reference's broadcast form (small inputs, tests and baselines)
+  ContrastiveHardestNegativeLoss   the argmin from torchpoints.feature_nn, the mined distance recomputed differentiably from
+                                   torchpoints.gather_rows: the (P, S, C) tensor never exists; pair keys, `isin` and the masked
+                                   means stay on the device (nothing is read back inside the training step)
+  BatchHardContrastiveLoss         the per-pair Python loop as one feature_nn call with the spatial exclusion
+  get_matches, estimate_transfo, fast_global_registration   utils/registration.py (1-NN by feature_nn, FGR by torchpoints.fgr)
+  compute_hit_ratio, compute_transfo_error, compute_scaled_registration_error, compute_registration_recall
+  evaluate_pair                    the tracker's sequence for one fragment pair (registration_tracker.py:123-145)
+  FragmentDescriptor               backbone -> FC_layer head (FragmentKPConv's layout) -> unit rows; "match" mode loss
+
+Not served: MS-SVConv (its configs open with a kernel_size 5 convolution), RANSAC (open3d), TEASER++, the Minkowski and
+patch models, and compute_loss_label's pytorch_metric_learning miners.
+"""
+import math
+
+import torch
+from torch import nn
+
+from . import torchpoints as tp
+from .kpconv_blocks import FastBatchNorm1d
+
+
+def pdist(A, B, dist_type="L2"):
+    """metric_losses.py:22-29: the (len(A), len(B)) distances from the broadcast difference"""
+    D2 = torch.sum((A.unsqueeze(1) - B.unsqueeze(0)).pow(2), 2)
+    if dist_type == "L2":
+        return torch.sqrt(D2 + 1e-7)
+    if dist_type == "SquareL2":
+        return D2
+    raise NotImplementedError("Not implemented")
+
+
+def _draw(n, k, device, generator):
+    """k of n rows without replacement, on the device"""
+    return torch.randperm(n, device=device, generator=generator)[:k]
+
+
+def _masked_mean(values, mask):
+    """values[mask].mean() without the boolean index (no device read): NaN for an empty mask, like the mean of nothing"""
+    zero = torch.zeros((), dtype=values.dtype, device=values.device)
+    return torch.where(mask, values, zero).sum() / mask.sum().to(values.dtype)
+
+
+def _isin(keys, sorted_table):
+    """np.isin(keys, table) for int64 keys against an ascending table, by binary search (torch.isin removes duplicates first
+    and reads their number back)"""
+    if sorted_table.numel() == 0:
+        return torch.zeros_like(keys, dtype=torch.bool)
+    at = torch.searchsorted(sorted_table, keys).clamp(max=sorted_table.numel() - 1)
+    return sorted_table[at] == keys
+
+
+class ContrastiveHardestNegativeLoss(nn.Module):
+    """metric_losses.py:32-119 (after FCGF): pos_loss = relu(|f0 - f1|^2 - pos_thresh).mean() over the sampled positive
+    pairs; for every sampled pair the nearest of `num_hn_samples` drawn rows of the other fragment is mined on each side,
+    neg = relu(neg_thresh - sqrt(d^2 + 1e-7))^2 averaged over the rows whose mined pair is not one of the positive pairs;
+    loss = pos_loss + (neg0 + neg1) / 2.
+
+    forward(F0, F1, matches, xyz0=None, xyz1=None, *, sel0=None, sel1=None, pos_sel=None): F0 (N0, C), F1 (N1, C), matches
+    (M, 2) rows of (F0, F1).  sel0 / sel1: the mined rows of F0 / F1, pos_sel: the sampled positive pairs (used when
+    M > num_pos, as in the reference); by default drawn with torch.randperm on the device (`generator` of the constructor),
+    where the reference draws np.random.choice on the host.  If every mined pair is a positive pair the mean over nothing is
+    NaN, as in the reference."""
+
+    def __init__(self, pos_thresh, neg_thresh, num_pos=5192, num_hn_samples=2048, generator=None):
+        super().__init__()
+        self.pos_thresh = pos_thresh
+        self.neg_thresh = neg_thresh
+        self.num_pos = num_pos
+        self.num_hn_samples = num_hn_samples
+        self.generator = generator
+
+    def contrastive_hardest_negative_loss(self, F0, F1, positive_pairs, sel0=None, sel1=None, pos_sel=None):
+        dev = F0.device
+        N0, N1 = len(F0), len(F1)
+        positive_pairs = positive_pairs.to(dev).long()
+        hash_seed = max(N0, N1)
+        sel0 = _draw(N0, min(N0, self.num_hn_samples), dev, self.generator) if sel0 is None else sel0.to(dev).long()
+        sel1 = _draw(N1, min(N1, self.num_hn_samples), dev, self.generator) if sel1 is None else sel1.to(dev).long()
+        sample_pos_pairs = positive_pairs
+        if len(positive_pairs) > self.num_pos:
+            if pos_sel is None:
+                pos_sel = _draw(len(positive_pairs), self.num_pos, dev, self.generator)
+            sample_pos_pairs = positive_pairs[pos_sel.to(dev).long()]
+        pos_ind0, pos_ind1 = sample_pos_pairs[:, 0], sample_pos_pairs[:, 1]
+        posF0, posF1 = tp.gather_rows(F0, pos_ind0), tp.gather_rows(F1, pos_ind1)
+
+        # the hardest negative of every positive row among the drawn rows of the other side: indices only
+        F0d, F1d = F0.detach(), F1.detach()
+        D01ind = sel1[tp.feature_nn(posF0, F1d[sel1])[1]]
+        D10ind = sel0[tp.feature_nn(posF1, F0d[sel0])[1]]
+        # ... and its distance again, differentiably, from the two gathered rows
+        D01min = torch.sqrt((posF0 - tp.gather_rows(F1, D01ind)).pow(2).sum(1) + 1e-7)
+        D10min = torch.sqrt((posF1 - tp.gather_rows(F0, D10ind)).pow(2).sum(1) + 1e-7)
+
+        pos_keys = torch.sort(positive_pairs[:, 0] + positive_pairs[:, 1] * hash_seed)[0]
+        mask0 = torch.logical_not(_isin(pos_ind0 + D01ind * hash_seed, pos_keys))
+        mask1 = torch.logical_not(_isin(D10ind + pos_ind1 * hash_seed, pos_keys))
+        pos_loss = torch.relu((posF0 - posF1).pow(2).sum(1) - self.pos_thresh)
+        neg_loss0 = _masked_mean(torch.relu(self.neg_thresh - D01min).pow(2), mask0)
+        neg_loss1 = _masked_mean(torch.relu(self.neg_thresh - D10min).pow(2), mask1)
+        return pos_loss.mean(), (neg_loss0 + neg_loss1) / 2
+
+    def forward(self, F0, F1, matches, xyz0=None, xyz1=None, *, sel0=None, sel1=None, pos_sel=None):
+        pos_loss, neg_loss = self.contrastive_hardest_negative_loss(F0, F1, matches, sel0, sel1, pos_sel)
+        return pos_loss + neg_loss
+
+
+class BatchHardContrastiveLoss(nn.Module):
+    """metric_losses.py:122-162, its arithmetic kept: the positive term is relu(max over the CHANNELS of (f0 - f1)^2 -
+    pos_thresh)^2, averaged; the negative of pair i is the nearest posF1 row (squared distance, no root) among the pairs
+    whose F0 point lies further than min_dist from pair i's, relu(neg_thresh - d2)^2 / len(pairs), summed.  The reference's
+    loop over the pairs is one feature_nn call with the spatial exclusion.  A pair with no allowed negative contributes 0
+    (the reference raises on the minimum of nothing)."""
+
+    def __init__(self, pos_thresh, neg_thresh, min_dist=0.15):
+        super().__init__()
+        self.pos_thresh = pos_thresh
+        self.neg_thresh = neg_thresh
+        self.min_dist = min_dist
+
+    def forward(self, F0, F1, positive_pairs, xyz0=None, xyz1=None):
+        if xyz0 is None:
+            raise ValueError("BatchHardContrastiveLoss needs xyz0 (the positions of F0's rows)")
+        positive_pairs = positive_pairs.to(F0.device).long()
+        posF0 = tp.gather_rows(F0, positive_pairs[:, 0])
+        posF1 = tp.gather_rows(F1, positive_pairs[:, 1])
+        subxyz0 = xyz0[positive_pairs[:, 0]]
+        hardest = tp.feature_nn(posF0, posF1, subxyz0, subxyz0, self.min_dist)[1]
+        found = hardest >= 0
+        closest_neg = (posF0 - tp.gather_rows(posF1, hardest.clamp(min=0))).pow(2).sum(1)
+        neg_terms = torch.relu(self.neg_thresh - closest_neg).pow(2) / len(posF0)
+        neg_loss = torch.where(found, neg_terms, torch.zeros_like(neg_terms)).sum()
+        furthest_pos = (posF0 - posF1).pow(2).max(1)[0]
+        pos_loss = torch.relu(furthest_pos - self.pos_thresh).pow(2)
+        return pos_loss.mean() + neg_loss
+
+
+# ------------------------------------------------------------------------------------------------ matching and pose solve
+def get_matches(feat_source, feat_target, sym=False):
+    """(M, 2) int64: every source row with its nearest target row in feature space (utils/registration.py:13-21, whose
+    torch_geometric knn is feature_nn here); sym=True keeps the mutual nearest neighbours only."""
+    nearest = tp.feature_nn(feat_source, feat_target)[1]
+    rows = torch.arange(len(nearest), device=nearest.device)
+    matches = torch.stack([rows, nearest], 1)
+    if sym:
+        back = tp.feature_nn(feat_target, feat_source)[1]
+        return matches[back[nearest] == rows]
+    return matches
+
+
+def estimate_transfo(xyz, xyz_target):
+    """Kabsch (utils/registration.py:24-43): the (4, 4) pose that maps xyz onto xyz_target in the least-squares sense"""
+    assert xyz.shape == xyz_target.shape
+    xyz_c = xyz - xyz.mean(0)
+    xyz_target_c = xyz_target - xyz_target.mean(0)
+    Q = xyz_c.T.mm(xyz_target_c) / len(xyz)
+    U, S, V = torch.svd(Q)
+    diag = torch.ones(3, dtype=xyz.dtype, device=xyz.device)
+    diag[2] = torch.det(V.mm(U.T))
+    R = V.mm(torch.diag(diag)).mm(U.T)
+    T = torch.eye(4, dtype=xyz.dtype, device=xyz.device)
+    T[:3, :3] = R
+    T[:3, 3] = xyz_target.mean(0) - R @ xyz.mean(0)
+    return T
+
+
+def fast_global_registration(xyz, xyz_target, mu_init=1, num_iter=20):
+    """utils/registration.py:83-103 through torchpoints.fgr (two launches per iteration, no (3N, 6) matrix, no host read)"""
+    assert xyz.shape == xyz_target.shape
+    return tp.fgr(xyz, xyz_target, mu_init=float(mu_init), num_iter=num_iter)
+
+
+# ------------------------------------------------------------------------------------------------------------------ metrics
+def compute_hit_ratio(xyz, xyz_target, T_gt, tau_1):
+    """the share of correspondences closer than tau_1 under T_gt (registration_metrics.py:30-37)"""
+    assert xyz.shape == xyz_target.shape
+    dist = torch.norm(xyz.mm(T_gt[:3, :3].T) + T_gt[:3, 3] - xyz_target, dim=1)
+    return torch.mean((dist < tau_1).to(torch.float))
+
+
+def compute_transfo_error(T_gt, T_pred):
+    """(translation error, rotation error in degrees) (registration_metrics.py:40-50)"""
+    rte = torch.norm(T_gt[:3, 3] - T_pred[:3, 3])
+    cos_theta = (torch.trace(T_gt[:3, :3].mm(T_pred[:3, :3].T)) - 1) * 0.5
+    cos_theta = torch.clamp(cos_theta, -1.0, 1.0)
+    rre = torch.acos(cos_theta) * 180 / math.pi
+    return rte, rre
+
+
+def compute_scaled_registration_error(xyz, T_gt, T_est, tol=1e-12):
+    """registration_metrics.py:53-66 (https://arxiv.org/pdf/2003.12841.pdf)"""
+    xyz_est = xyz @ T_est[:3, :3].T + T_est[:3, 3]
+    xyz_gt = xyz @ T_gt[:3, :3].T + T_gt[:3, 3]
+    centroid = xyz_est.mean(0)
+    dist1 = torch.sqrt(torch.sum((xyz_est - xyz_gt) ** 2, -1))
+    dist2 = torch.sqrt(torch.sum((xyz_est - centroid) ** 2, -1))
+    return torch.mean(dist1 / (dist2 + tol))
+
+
+def compute_registration_recall(xyz_gt, xyz_target_gt, T_est, thresh=0.2):
+    """registration_metrics.py:69-76: whether the mean distance of the true correspondences under T_est is below thresh.
+    A boolean scalar on the inputs' device (the reference reads it back with .item())."""
+    dist = torch.norm(xyz_gt @ T_est[:3, :3].T + T_est[:3, 3] - xyz_target_gt, dim=1)
+    return dist.mean() < thresh
+
+
+def evaluate_pair(feat, feat_target, xyz, xyz_target, matches_gt, num_points=5000, tau_1=0.1, tau_2=0.05, rand=None,
+                  rand_target=None):
+    """What FragmentRegistrationTracker.track does for one fragment pair (registration_tracker.py:123-145): the pose of the
+    true matches by Kabsch, 1-NN feature matches between `num_points` drawn rows of each side (rand / rand_target: the
+    drawn rows, default torch.randperm on the device), FGR on the matched positions, and the tracker's figures as a dict of
+    device scalars: hit_ratio, feat_match_ratio (hit_ratio > tau_2), trans_error, rot_error, sr_err."""
+    dev = feat.device
+    if rand is None:
+        rand = torch.randperm(len(feat), device=dev)[:num_points]
+    if rand_target is None:
+        rand_target = torch.randperm(len(feat_target), device=dev)[:num_points]
+    matches_gt = matches_gt.to(dev).long()
+    T_gt = estimate_transfo(xyz[matches_gt[:, 0]], xyz_target[matches_gt[:, 1]])
+    matches_pred = get_matches(feat[rand], feat_target[rand_target])
+    src = xyz[rand][matches_pred[:, 0]]
+    tgt = xyz_target[rand_target][matches_pred[:, 1]]
+    T_pred = fast_global_registration(src, tgt)
+    hit_ratio = compute_hit_ratio(src, tgt, T_gt, tau_1)
+    trans_error, rot_error = compute_transfo_error(T_pred, T_gt)
+    sr_err = compute_scaled_registration_error(xyz, T_gt, T_pred)
+    return {"hit_ratio": hit_ratio, "feat_match_ratio": (hit_ratio > tau_2).to(torch.float), "trans_error": trans_error,
+            "rot_error": rot_error, "sr_err": sr_err}
+
+
+# -------------------------------------------------------------------------------------------------------------------- model
+class FragmentDescriptor(nn.Module):
+    """Per-point descriptors of a fragment (FragmentKPConv, models/registration/kpconv.py:127-245; FragmentBaseModel,
+    base.py:77-138, in "match" mode).  `backbone`: any module with an `output_nc` attribute that maps the batch to (N, C)
+    features or to a batch object whose `.x` holds them.  The head carries FragmentKPConv's names: FC_layer.<i> = Linear
+    without bias - FastBatchNorm1d - LeakyReLU(0.2) for mlp_nn[i - 1] -> mlp_nn[i], an optional FC_layer.Dropout, and
+    FC_layer.Last = Linear(mlp_nn[-1], out_channels) without bias; rows are divided by (norm + eps) when
+    normalize_feature.  metric_loss: a module called as (F0, F1, matches, xyz0, xyz1), e.g. the two losses above.
+
+    forward(data, data_target=None, match=None): `output`; with a target and `match` (M, 2) also `output_target` and
+    `loss`.  `data.pos` is handed to the loss as the positions."""
+
+    def __init__(self, backbone, mlp_nn, out_channels=32, normalize_feature=True, eps=1e-3, bn_momentum=0.02, dropout=0,
+                 metric_loss=None):
+        super().__init__()
+        if len(mlp_nn) < 1 or mlp_nn[0] != backbone.output_nc:
+            raise ValueError("mlp_nn must start with the backbone's output_nc (%d)" % backbone.output_nc)
+        self.backbone = backbone
+        self.out_channels = out_channels
+        self.FC_layer = nn.Sequential()
+        in_feat = mlp_nn[0]
+        for i in range(1, len(mlp_nn)):
+            self.FC_layer.add_module(str(i), nn.Sequential(nn.Linear(in_feat, mlp_nn[i], bias=False),
+                                                           FastBatchNorm1d(mlp_nn[i], momentum=bn_momentum),
+                                                           nn.LeakyReLU(0.2)))
+            in_feat = mlp_nn[i]
+        if dropout:
+            self.FC_layer.add_module("Dropout", nn.Dropout(p=dropout))
+        self.FC_layer.add_module("Last", nn.Linear(in_feat, out_channels, bias=False))
+        self.normalize_feature = normalize_feature
+        self.eps = eps
+        self.metric_loss_module = metric_loss
+        self.output = self.output_target = self.loss = None
+
+    @classmethod
+    def sparse(cls, input_nc, in_feat=32, mlp_nn=None, eps=1e-20, **kwargs):
+        """the sparse voxel U-Net (SparseConv3dUnet("unet_4")) under the head; eps as in models/registration/spconv3d.py"""
+        from .sparseconv import SparseConv3dUnet
+        backbone = SparseConv3dUnet("unet_4", input_nc, in_feat=in_feat)
+        nc = backbone.output_nc
+        return cls(backbone, [nc, nc] if mlp_nn is None else mlp_nn, eps=eps, **kwargs)
+
+    @classmethod
+    def kpconv(cls, input_nc, in_feat=64, in_grid_size=0.02, num_layers=4, mlp_nn=None, **kwargs):
+        """the KPConv U-Net (applications KPConv(architecture="unet")) under the head, conf/models/registration/kpconv.yaml"""
+        from .kpconv_unet import KPConv
+        backbone = KPConv("unet", input_nc=input_nc, num_layers=num_layers, in_feat=in_feat, in_grid_size=in_grid_size)
+        nc = backbone.output_nc
+        return cls(backbone, [nc, nc] if mlp_nn is None else mlp_nn, **kwargs)
+
+    def apply_nn(self, data):
+        out = self.backbone(data)
+        feats = out if torch.is_tensor(out) else out.x
+        output = self.FC_layer(feats)
+        if self.normalize_feature:
+            return output / (torch.norm(output, p=2, dim=1, keepdim=True) + self.eps)
+        return output
+
+    def forward(self, data, data_target=None, match=None):
+        self.output = self.apply_nn(data)
+        self.output_target = self.loss = None
+        if data_target is None or match is None:
+            return self.output
+        self.output_target = self.apply_nn(data_target)
+        if self.metric_loss_module is None:
+            raise ValueError("a target and matches were given but the model has no metric_loss")
+        self.loss = self.metric_loss_module(self.output, self.output_target, match[:, :2], getattr(data, "pos", None),
+                                            getattr(data_target, "pos", None))
+        return self.output
+
+    def get_output(self):
+        return self.output, self.output_target

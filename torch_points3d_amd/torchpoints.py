@@ -19,7 +19,8 @@ from . import _lib
 
 __all__ = ["furthest_point_sample", "ball_query", "three_nn", "three_interpolate", "grouping_operation"]
 # (message-passing side: fps_quota, fps_ragged, radius_edges, pointconv_rows, segment_max, rsconv_relation_rows,
-# rsconv_msgmax; PointGroup's clustering: ClusterSet, region_grow_csr -- further down)
+# rsconv_msgmax; PointGroup's clustering: ClusterSet, region_grow_csr; registration: feature_nn, gather_rows, fgr --
+# further down)
 
 
 def _dev(*tensors):
@@ -762,3 +763,123 @@ def region_grow_csr(pos, labels, batch, ignore_labels=(), radius=0.03, nsample=3
                        min_cluster_size=min_cluster_size)
         return ClusterSet.from_list([torch.sort(c)[0] for c in found], device=dev, labels=lab, batch=bat, route="host")
     return ClusterSet(members[:M], starts[:K + 1], member_cluster[:M], label[:K], cloud[:K], "device")
+
+
+# ------------------------------------------------------------------------------------------- registration (csrc/registration.hip)
+def feature_nn(a, b, pos_a=None, pos_b=None, min_dist=None):
+    """The nearest row of b (S, C) for every row of a (P, C) in feature space: (dist2 (P,) fp32, idx (P,) int64) with
+    dist2[i] = min_j sum_c (a[i, c] - b[j, c])^2 in the difference form and idx[i] the lowest such j among exact ties.
+    With pos_a (P, 3), pos_b (S, 3) and min_dist, j is a candidate only if sqrt(|pos_a[i] - pos_b[j]|^2 + 1e-7) > min_dist
+    (`pdist(pos_a, pos_b) > min_dist` of core/losses/metric_losses.py).  A row without a candidate gets idx -1 and
+    dist2 +inf.  Index-valued: no gradient (gather_rows recomputes a mined distance differentiably).  Repeats are
+    bit-equal.  Device tensors only."""
+    masked = pos_a is not None or pos_b is not None or min_dist is not None
+    if masked and (pos_a is None or pos_b is None or min_dist is None):
+        raise ValueError("pos_a, pos_b and min_dist go together")
+    dev = _dev(a, b, pos_a, pos_b)
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.shape[1] < 1:
+        raise ValueError("a must be (P, C) and b (S, C) with C >= 1")
+    a, b = _f32(a), _f32(b)
+    P, C = a.shape
+    S = b.shape[0]
+    if masked:
+        pos_a, pos_b = _f32(pos_a), _f32(pos_b)
+        if tuple(pos_a.shape) != (P, 3) or tuple(pos_b.shape) != (S, 3):
+            raise ValueError("pos_a must be (P, 3) and pos_b (S, 3)")
+    dist2 = torch.empty((P,), dtype=torch.float32, device=dev)
+    idx = torch.empty((P,), dtype=torch.int64, device=dev)
+    if P == 0:
+        return dist2, idx
+    nbytes = _lib.load().tp3d_feature_nn_workspace_bytes(P, S, C)
+    if S > 0 and nbytes == 0:
+        raise ValueError("feature_nn: %d x %d rows are not served" % (P, S))
+    ws = _lib.workspace("feature_nn", nbytes, dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_feature_nn_f32", _lib.ptr(a), _lib.ptr(b), _lib.ptr(pos_a), _lib.ptr(pos_b), P, S, C,
+                  float(min_dist) if masked else 0.0, _lib.ptr(dist2), _lib.ptr(idx), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+    return dist2, idx
+
+
+def _invert_rows(idx, n_rows):
+    """(start (n_rows + 1,), order (len(idx),)) int32 of tp3d_pv_invert_i32 for a (N,) table of rows"""
+    dev = idx.device
+    N = idx.shape[0]
+    table = idx.to(torch.int32).reshape(N, 1).contiguous()
+    start = torch.empty((n_rows + 1,), dtype=torch.int32, device=dev)
+    order = torch.empty((max(N, 1),), dtype=torch.int32, device=dev)
+    nbytes = _lib.load().tp3d_pv_invert_workspace_bytes(N, 1)
+    ws = _lib.workspace("pv_invert", nbytes, dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_pv_invert_i32", _lib.ptr(table), N, 1, int(n_rows), _lib.ptr(start), _lib.ptr(order), _lib.ptr(ws), nbytes,
+                  _lib.stream_ptr(dev))
+    return start, order
+
+
+class _GatherRows(torch.autograd.Function):
+    """out[p] = x[idx[p]]; backward: dx[v] = the sum of dy[p] over the p with idx[p] == v in ascending p (the ordered run sum
+    over the inverted index: no float atomics)"""
+
+    @staticmethod
+    def forward(ctx, x, idx):
+        xc = _f32(x)
+        table = idx.to(torch.int32).reshape(-1, 1).contiguous()
+        out = torch.empty((table.shape[0], xc.shape[1]), dtype=torch.float32, device=xc.device)
+        with _lib.on_device(xc.device):
+            _lib.call("tp3d_pv_gather_f32", _lib.ptr(xc), _lib.ptr(table), None, None, table.shape[0], 1, xc.shape[0], xc.shape[1],
+                      _lib.ptr(out), _lib.stream_ptr(xc.device))
+        ctx.save_for_backward(idx)
+        ctx.n_rows = xc.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        (idx,) = ctx.saved_tensors
+        dy = _f32(dy)
+        dev = dy.device
+        dx = torch.empty((ctx.n_rows, dy.shape[1]), dtype=torch.float32, device=dev)
+        if ctx.n_rows == 0:
+            return dx, None
+        if idx.numel() == 0:
+            return dx.zero_(), None
+        start, order = _invert_rows(idx, ctx.n_rows)
+        with _lib.on_device(dev):
+            _lib.call("tp3d_pv_runsum_f32", _lib.ptr(dy), _lib.ptr(start), _lib.ptr(order), None, None, ctx.n_rows, 1, dy.shape[0],
+                      dy.shape[1], _lib.ptr(dx), _lib.stream_ptr(dev))
+        return dx, None
+
+
+def gather_rows(x, idx):
+    """x[idx] for x (R, C) fp32 and idx (N,) rows of x, differentiable wrt x.  The gradient of a row that idx names several
+    times is summed in ascending position (tp3d_pv_invert_i32 + tp3d_pv_runsum_f32), so it is bit-equal run to run; rows
+    idx does not name get zeros.  An index outside [0, R) reads as a row of zeros and receives no gradient."""
+    _dev(x, idx)
+    if x.dim() != 2 or idx.dim() != 1 or x.shape[1] < 1:
+        raise ValueError("x must be (R, C) with C >= 1 and idx (N,)")
+    if idx.numel() == 0 or x.shape[0] == 0:
+        return x.new_zeros((idx.numel(), x.shape[1]), dtype=torch.float32) + 0.0 * x.sum()
+    return _GatherRows.apply(x, idx)
+
+
+def fgr(xyz, xyz_target, mu_init=1.0, num_iter=20):
+    """Fast Global Registration (utils/registration.py:83-103) of the correspondences xyz[i] <-> xyz_target[i], both (N, 3):
+    the (4, 4) fp32 pose T with xyz_target ~ xyz @ T[:3, :3].T + T[:3, 3].  Two launches per iteration (the normal equations
+    summed per block in double; one wave that solves them, forms the Rodrigues update, composes the pose and keeps mu's
+    schedule): the (3N, 6) matrix is never stored and the host reads nothing back.  The pose is carried in double and
+    applied to the input points (the reference re-transforms its fp32 copy every iteration).  An iteration whose system
+    has a pivot that is exactly 0, or no finite solution, leaves the pose as it was (torch.linalg.solve raises there)."""
+    dev = _dev(xyz, xyz_target)
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape != xyz_target.shape:
+        raise ValueError("xyz and xyz_target must both be (N, 3)")
+    xyz, xyz_target = _f32(xyz), _f32(xyz_target)
+    N = xyz.shape[0]
+    T = torch.eye(4, dtype=torch.float32, device=dev)
+    nbytes = _lib.load().tp3d_fgr_workspace_bytes(N)
+    if nbytes == 0:
+        raise ValueError("fgr: %d correspondences are not served" % N)
+    ws = _lib.workspace("fgr", nbytes, dev)
+    stream = _lib.stream_ptr(dev)
+    with _lib.on_device(dev):
+        for i in range(int(num_iter)):
+            _lib.call("tp3d_fgr_accumulate_f32", _lib.ptr(xyz), _lib.ptr(xyz_target), N, i, _lib.ptr(ws), nbytes, stream)
+            _lib.call("tp3d_fgr_solve", N, i, float(mu_init), _lib.ptr(T), _lib.ptr(ws), nbytes, stream)
+    return T
