@@ -589,14 +589,23 @@ int tp3d_rsconv_msgmax_bwd_f32(const float *dout, const int64_t *arg, const floa
  *     down > 0: the distinct floor(c / down) * down per axis (batch kept), ascending (batch, x, y, z): keys_out, rows_out
  *     (= iota) and coords_out (., 4) sized for N rows, meta[8] of them written.
  *   tp3d_sparse_kmap_i32: table (Nq, ksize^3) int32 = the row of the set's voxel at qcoords[q] + sign * offset_k * step, -1
- *     where absent; offsets {-1, 0, 1} (ksize 3), {0, 1} (ksize 2), {0} (ksize 1) per axis, x slowest, z fastest.
+ *     where absent; offsets {-(k / 2) .. k / 2} (ksize 3 or 5), {0, 1} (ksize 2), {0} (ksize 1) per axis, x slowest, z
+ *     fastest.  The convolution and weight gradient take K <= 125.
  *   tp3d_sparse_kmap_mirror_i32: inverse[i][k] = forward[i][K - 1 - k] (stride 1, odd kernel).
  *   tp3d_sparse_conv_f32: y (Nout, Cout) = sum_k x[table[r][k]] . W[k], x (Nsrc, Cin); W (K, Cin, Cout), or with
  *     w_transposed != 0 W is (K, Cout, Cin) and W[k]^T is applied.  An entry outside [0, Nsrc) counts as absent.  fp32
  *     MFMA over LDS-staged gathered rows; Cin <= 4 plain FMA.  No atomics: bit-reproducible.
  *   tp3d_sparse_wgrad_f32: dW (K, Cin, Cout) = sum_r x[table[r][k]]^T . dy[r], x (Nsrc, Cin), dy (N, Cout), table (N, K);
  *     tp3d_sparse_wgrad_chunks(N, K, Cin, Cout) row chunks, each summed in ascending row order, their partials
- *     (workspace: tp3d_sparse_wgrad_workspace_floats, 0 for one chunk) summed in ascending chunk order. */
+ *     (workspace: tp3d_sparse_wgrad_workspace_floats, 0 for one chunk) summed in ascending chunk order.
+ *   The wide first layer, 27 < K <= 125 and Cin <= 4 (a 5^3 kernel on a surface finds few of its offsets):
+ *   tp3d_sparse_conv_wide_f32: the sum of tp3d_sparse_conv_f32 (W (K, Cin, Cout) only) over the PRESENT offsets of a row,
+ *     compacted per wave with a ballot, k then ci ascending; W staged in LDS.  tp3d_sparse_conv_wide_serves is 0 where W
+ *     and the hit lists do not fit the LDS (TP3D_E_BADARG from the launch): the generic kernel serves those.
+ *   tp3d_sparse_wgrad_wide_f32: dW as tp3d_sparse_wgrad_f32; a workgroup per row chunk, per-wave accumulators in LDS (no
+ *     atomics), rows of a wave, then waves, then chunks summed in ascending order: bit-reproducible.  Each dy row and table
+ *     row is read once.  tp3d_sparse_wgrad_wide_chunks is 0 (and the launch TP3D_E_BADARG) where one wave's K * Cin * Cout
+ *     accumulators do not fit the LDS; workspace: tp3d_sparse_wgrad_wide_workspace_floats, 0 for one chunk. */
 size_t tp3d_sparse_workspace_bytes(int64_t N);
 int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int ts, int down, int64_t *keys_out, int32_t *rows_out,
                               int32_t *coords_out, int32_t *meta, void *workspace, size_t workspace_bytes, void *stream);
@@ -609,6 +618,28 @@ int tp3d_sparse_wgrad_chunks(int64_t N, int K, int Cin, int Cout);
 size_t tp3d_sparse_wgrad_workspace_floats(int64_t N, int K, int Cin, int Cout);
 int tp3d_sparse_wgrad_f32(const float *x, const float *dy, const int32_t *table, int64_t N, int64_t Nsrc, int K, int Cin,
                           int Cout, float *dW, float *workspace, size_t workspace_floats, void *stream);
+int tp3d_sparse_conv_wide_serves(int K, int Cin, int Cout);
+int tp3d_sparse_conv_wide_f32(const float *x, const int32_t *table, const float *W, int64_t Nout, int64_t Nsrc, int K, int Cin,
+                              int Cout, float *y, void *stream);
+int tp3d_sparse_wgrad_wide_chunks(int64_t N, int K, int Cin, int Cout);
+size_t tp3d_sparse_wgrad_wide_workspace_floats(int64_t N, int K, int Cin, int Cout);
+int tp3d_sparse_wgrad_wide_f32(const float *x, const float *dy, const int32_t *table, int64_t N, int64_t Nsrc, int K, int Cin,
+                               int Cout, float *dW, float *workspace, size_t workspace_floats, void *stream);
+
+/* Multi-scale fusion (csrc/scale_fuse.hip)                        [models/registration/ms_svconv3d.py apply_nn]
+ *   xs, dxs: HOST arrays of S <= 8 device pointers, each (N, C) fp32.  xhat_s = x_s / (||x_s||_2 + eps) per row; mode 0 cat:
+ *   out (N, S * C), scale s in columns [s C, (s + 1) C); mode 1 max, 2 mean over the scales: out (N, C).  norm (N, S) =
+ *   ||x_s||_2 (read by the backward); xhat (S, N, C) or NULL: the normalised rows (modes 1, 2); arg (N, C) uint8 = the
+ *   winning scale, ties to the lowest (mode 1 only, else NULL).  A group of 8 / 16 / 32 / 64 lanes owns a row; sums are
+ *   butterfly reductions in a fixed order.  No atomics: bit-reproducible.
+ *   tp3d_scale_fuse_bwd_f32: dxs[s] = g_s / d - x_s <g_s, x_s> / (n d^2), d = n + eps (evaluated as (g_s - h <g_s, h> d / n) / d,
+ *   h = x_s / d), and g_s / d where n == 0; g_s = the
+ *   cotangent of xhat_s: gout's columns (cat), gout / S (mean), gout where arg == s (max), plus gxhat[s] (S, N, C) when not
+ *   NULL; gout may be NULL (= 0). */
+int tp3d_scale_fuse_fwd_f32(const float *const *xs, int S, int64_t N, int C, int mode, float eps, float *out, float *xhat,
+                            float *norm, unsigned char *arg, void *stream);
+int tp3d_scale_fuse_bwd_f32(const float *const *xs, int S, int64_t N, int C, int mode, float eps, const float *gout,
+                            const float *gxhat, const float *norm, const unsigned char *arg, float *const *dxs, void *stream);
 
 /* Point-voxel operations of PVCNN (csrc/pointvoxel.hip)                                     [modules/PVCNN/utils.py]
  *   Features fp32, tables int32, -1 = absent; an index outside its row range counts as absent.  No float atomics: every

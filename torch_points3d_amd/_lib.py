@@ -87,6 +87,10 @@ SIGNATURES = {
     "tp3d_sparse_kmap_mirror_i32": [_p, _l, _i, _p, _p],
     "tp3d_sparse_conv_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _i, _p, _p],
     "tp3d_sparse_wgrad_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
+    "tp3d_sparse_conv_wide_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _p, _p],
+    "tp3d_sparse_wgrad_wide_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
+    "tp3d_scale_fuse_fwd_f32": [_p, _i, _l, _i, _i, _f, _p, _p, _p, _p, _p],
+    "tp3d_scale_fuse_bwd_f32": [_p, _i, _l, _i, _i, _f, _p, _p, _p, _p, _p, _p],
     "tp3d_pv_quantize_f32": [_p, _l, _i, _p, _p],
     "tp3d_pv_trilinear_f32": [_p, _p, _l, _l, _i, _i, _p, _p],
     "tp3d_pv_invert_i32": [_p, _l, _i, _l, _p, _p, _p, ctypes.c_size_t, _p],
@@ -132,6 +136,9 @@ MISC = {
     "tp3d_sparse_workspace_bytes": (_z, [_l]),
     "tp3d_sparse_wgrad_chunks": (_i, [_l, _i, _i, _i]),
     "tp3d_sparse_wgrad_workspace_floats": (_z, [_l, _i, _i, _i]),
+    "tp3d_sparse_conv_wide_serves": (_i, [_i, _i, _i]),
+    "tp3d_sparse_wgrad_wide_chunks": (_i, [_l, _i, _i, _i]),
+    "tp3d_sparse_wgrad_wide_workspace_floats": (_z, [_l, _i, _i, _i]),
     "tp3d_pv_invert_workspace_bytes": (_z, [_l, _i]),
     "tp3d_region_grow_workspace_bytes": (_z, [_l]),
     "tp3d_feature_nn_workspace_bytes": (_z, [_l, _l, _i]),

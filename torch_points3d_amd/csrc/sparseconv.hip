@@ -7,8 +7,8 @@
 // bounding box, so keys ascend in (batch, x, y, z) -- the row order of a stride-2 output set.
 //
 // A kernel map is two int32 tables built here by binary search: forward (Nout, K) = input row at coord(o) + offset_k,
-// inverse (Nin, K) = output row o with coord(o) + offset_k == coord(i); -1 where absent.  Offsets: odd k {-1,0,1} * ts,
-// k = 2 {0,1} * ts per axis, x slowest, z fastest.  Every product is y[r] = sum_k x[table[r][k]] . W[k]: gathered rows and
+// inverse (Nin, K) = output row o with coord(o) + offset_k == coord(i); -1 where absent.  Offsets: odd k {-(k/2)..k/2} * ts
+// (k = 3 or 5), k = 2 {0,1} * ts per axis, x slowest, z fastest.  Every product is y[r] = sum_k x[table[r][k]] . W[k]: gathered rows and
 // the W[k] tile are staged in LDS, contracted with v_mfma_f32_16x16x4_f32, accumulators stay in registers across k;
 // nothing of size N*K*C is written to memory.  The gather also range-checks every index against the source row count.
 // No float atomics: forward, dX and dW are bit-reproducible.
@@ -20,6 +20,7 @@ constexpr int SP_BLOCK = SK_BLOCK;
 constexpr int SP_COORD_LIMIT = 1 << 18;  // |coord| below this at tensor stride 1
 constexpr int SP_BATCH_LIMIT = 1 << 9;   // batch below this
 constexpr int SP_META = 16;
+constexpr int SP_KMAX = 125;  // offsets of the widest kernel served (5^3)
 constexpr int SP_BAD_RANGE = 1, SP_BAD_DUP = 2, SP_BAD_SPAN = 4;
 
 typedef float sp_f32x4 __attribute__((ext_vector_type(4)));
@@ -376,6 +377,148 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_wgrad_kernel(const float *__restr
     }
 }
 
+// ------------------------------------------------------------------------- wide first layer (Cin <= 4, 27 < K <= 125)
+// A 5^3 kernel on a scanned surface finds a small part of its 125 offsets.  A wave reads a row's table entries with two
+// coalesced loads, compacts the present ones (ascending k) into its own LDS list with a ballot and loops over the hits only.
+constexpr int SPW_HITS = 128;            // hit slots per row (K <= 125)
+constexpr int SPW_CT = 32;               // channels per pass: the lanes of a half-wave
+constexpr int SPW_MAX_CIN = 4;
+constexpr int SPW_LDS_MAX = 160 * 1024;  // LDS of a CU
+constexpr int SPW_FWD_ROWS = 2 * (SP_BLOCK / 64);  // rows per workgroup step: two per wave
+constexpr int SPW_FWD_MAX_BLOCKS = 512;
+constexpr int SPW_WG_ROWS = 128;         // least rows per weight-gradient chunk
+constexpr int SPW_WG_MAX_CHUNKS = 256;
+constexpr int SPW_WG_MAX_WAVES = 4;
+
+// the wave's own LDS writes have landed (each wave owns its hit lists and accumulators)
+__device__ __forceinline__ void sp_wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// hk[0..n), hi[0..n) = the offsets k (ascending) of row r with a source row in [0, Nsrc), and those rows; returns n
+// (wave-uniform).  r < 0: no row.
+__device__ __forceinline__ int spw_compact_row(const int *__restrict__ table, int64_t r, int K, int64_t Nsrc, int lane, int *hk,
+                                               int *hi)
+{
+    int t0 = -1, t1 = -1;
+    if (r >= 0) {
+        const int *row = table + r * K;
+        if (lane < K) t0 = row[lane];
+        if (lane + 64 < K) t1 = row[lane + 64];
+    }
+    if (t0 < 0 || t0 >= Nsrc) t0 = -1;
+    if (t1 < 0 || t1 >= Nsrc) t1 = -1;
+    const unsigned long long m0 = __ballot(t0 >= 0), m1 = __ballot(t1 >= 0);
+    const int n0 = __popcll(m0);
+    if (t0 >= 0) {
+        const int p = lanes_below(m0);
+        hk[p] = lane;
+        hi[p] = t0;
+    }
+    if (t1 >= 0) {
+        const int p = n0 + lanes_below(m1);
+        hk[p] = lane + 64;
+        hi[p] = t1;
+    }
+    return n0 + __popcll(m1);
+}
+
+// y[r][co] = sum over the present k (ascending), ci (ascending) of x[table[r][k]][ci] * W[k][ci][co].  W is staged in LDS
+// once per workgroup; a half-wave owns a row, its lanes are 32 output channels (wider layers take further passes).
+__global__ __launch_bounds__(SP_BLOCK) void sp_conv_wide_kernel(const float *__restrict__ x, const int *__restrict__ table,
+                                                                 const float *__restrict__ W, int64_t Nout, int64_t Nsrc, int K,
+                                                                 int Cin, int Cout, float *__restrict__ y)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, c = lane & 31;
+    const int KCC = K * Cin * Cout;
+    float *s_w = reinterpret_cast<float *>(smem);
+    int *s_hit = reinterpret_cast<int *>(s_w + KCC) + wave * 4 * SPW_HITS;  // [row of the wave][k | source row][slot]
+    for (int e = tid; e < KCC; e += SP_BLOCK) s_w[e] = W[e];
+    __syncthreads();
+    for (int64_t base = (int64_t)blockIdx.x * SPW_FWD_ROWS; base < Nout; base += (int64_t)gridDim.x * SPW_FWD_ROWS) {
+        const int64_t r0 = base + 2 * wave;
+        const int n0 = spw_compact_row(table, r0 < Nout ? r0 : -1, K, Nsrc, lane, s_hit, s_hit + SPW_HITS);
+        const int n1 = spw_compact_row(table, r0 + 1 < Nout ? r0 + 1 : -1, K, Nsrc, lane, s_hit + 2 * SPW_HITS, s_hit + 3 * SPW_HITS);
+        sp_wave_lds_sync();
+        const int64_t r = r0 + half;
+        const int n = half ? n1 : n0;
+        const int *hk = s_hit + 2 * half * SPW_HITS, *hi = hk + SPW_HITS;
+        for (int co = c; co < Cout; co += SPW_CT) {
+            float acc = 0.0f;
+            for (int h = 0; h < n; ++h) {
+                const float *xr = x + (int64_t)hi[h] * Cin;
+                const float *w = s_w + hk[h] * Cin * Cout + co;
+                for (int ci = 0; ci < Cin; ++ci) acc = __builtin_fmaf(xr[ci], w[ci * Cout], acc);
+            }
+            if (r < Nout) y[r * Cout + co] = acc;
+        }
+        sp_wave_lds_sync();  // the next step rewrites the hit lists
+    }
+}
+
+inline int64_t spw_wgrad_chunk_rows(int64_t N)
+{
+    int64_t rows = (N + SPW_WG_MAX_CHUNKS - 1) / SPW_WG_MAX_CHUNKS;
+    rows = (rows + 7) / 8 * 8;
+    return rows < SPW_WG_ROWS ? SPW_WG_ROWS : rows;
+}
+
+// waves per workgroup of the wide weight gradient: each owns K * Cin * Cout accumulators and one hit list in LDS; 0 when
+// not even one fits
+inline int spw_wgrad_waves(int K, int Cin, int Cout)
+{
+    const int64_t per_wave = (int64_t)K * Cin * Cout * 4 + 2 * SPW_HITS * 4;
+    const int64_t waves = SPW_LDS_MAX / per_wave;
+    return (int)(waves > SPW_WG_MAX_WAVES ? SPW_WG_MAX_WAVES : waves);
+}
+
+// out[chunk][k][ci][co] = sum over the chunk's rows of x[table[r][k]][ci] * dy[r][co].  One workgroup per chunk; a wave
+// takes a contiguous run of the chunk's rows in ascending order and adds into its own accumulators in LDS: lanes are 32
+// output channels x two hit slots, so a step updates two different k and no two lanes share an address.  The waves'
+// accumulators are then summed in wave order.  Every dy row and table row is read once; no atomics.
+__global__ __launch_bounds__(64 * SPW_WG_MAX_WAVES) void sp_wgrad_wide_kernel(const float *__restrict__ x, const float *__restrict__ dy, const int *__restrict__ table,
+                                     int64_t N, int64_t Nsrc, int K, int Cin, int Cout, int64_t chunk_rows,
+                                     float *__restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, slot = lane >> 5, c = lane & 31;
+    const int waves = blockDim.x >> 6;
+    const int KCC = K * Cin * Cout;
+    float *s_acc = reinterpret_cast<float *>(smem);
+    float *acc = s_acc + (int64_t)wave * KCC;
+    int *hk = reinterpret_cast<int *>(s_acc + (int64_t)waves * KCC) + wave * 2 * SPW_HITS, *hi = hk + SPW_HITS;
+    for (int e = lane; e < KCC; e += 64) acc[e] = 0.0f;
+    const int64_t rb = (int64_t)blockIdx.x * chunk_rows;
+    const int64_t re = min(N, rb + chunk_rows);
+    const int64_t per = (re - rb + waves - 1) / waves;
+    const int64_t wb = rb + wave * per, we = min(re, wb + per);
+    sp_wave_lds_sync();
+    for (int64_t r = wb; r < we; ++r) {
+        const int n = spw_compact_row(table, r, K, Nsrc, lane, hk, hi);
+        sp_wave_lds_sync();
+        for (int co = c; co < Cout; co += SPW_CT) {
+            const float g = dy[r * Cout + co];
+            for (int h = slot; h < n; h += 2) {
+                const float *xr = x + (int64_t)hi[h] * Cin;
+                float *a = acc + hk[h] * Cin * Cout + co;
+                for (int ci = 0; ci < Cin; ++ci) a[ci * Cout] = __builtin_fmaf(xr[ci], g, a[ci * Cout]);
+            }
+        }
+        sp_wave_lds_sync();  // the next row rewrites the hit list and may update the same accumulators from other lanes
+    }
+    __syncthreads();
+    float *o = out + (int64_t)blockIdx.x * KCC;
+    for (int e = tid; e < KCC; e += blockDim.x) {
+        float t = s_acc[e];
+        for (int w = 1; w < waves; ++w) t += s_acc[(int64_t)w * KCC + e];
+        o[e] = t;
+    }
+}
+
 // the sort covers the bits the key can have: the host knows the hard limits only (3 * 19 + 9 bits would pass 64, the
 // span flag rejects such a box), so 63
 constexpr unsigned SP_KEY_BITS = 63;
@@ -423,7 +566,7 @@ TP3D_EXPORT int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int 
 TP3D_EXPORT int tp3d_sparse_kmap_i32(const int32_t *qcoords, int64_t Nq, int ksize, int step, int sign, const int64_t *keys,
                                      const int32_t *rows, const int32_t *meta, int64_t Ns, int32_t *table, void *stream)
 {
-    if (Nq <= 0 || Ns <= 0 || ksize < 1 || ksize > 3 || step <= 0 || step >= SP_COORD_LIMIT || (sign != 1 && sign != -1) ||
+    if (Nq <= 0 || Ns <= 0 || ksize < 1 || ksize > 5 || ksize == 4 || step <= 0 || step >= SP_COORD_LIMIT || (sign != 1 && sign != -1) ||
         !qcoords || !keys || !rows || !meta || !table)
         return TP3D_E_BADARG;
     const int K = ksize * ksize * ksize;
@@ -446,7 +589,7 @@ TP3D_EXPORT int tp3d_sparse_kmap_mirror_i32(const int32_t *forward, int64_t N, i
 TP3D_EXPORT int tp3d_sparse_conv_f32(const float *x, const int32_t *table, const float *W, int64_t Nout, int64_t Nsrc, int K,
                                      int Cin, int Cout, int w_transposed, float *y, void *stream)
 {
-    if (Nout < 0 || Nsrc < 0 || K <= 0 || K > 27 || Cin <= 0 || Cout <= 0) return TP3D_E_BADARG;
+    if (Nout < 0 || Nsrc < 0 || K <= 0 || K > SP_KMAX || Cin <= 0 || Cout <= 0) return TP3D_E_BADARG;
     if (Nout == 0) return TP3D_OK;
     if (!table || !W || !y || (Nsrc > 0 && !x)) return TP3D_E_BADARG;
     if (Nout >= 0x7fffffff || Nsrc >= 0x7fffffff) return TP3D_E_TOOBIG;
@@ -485,7 +628,7 @@ TP3D_EXPORT size_t tp3d_sparse_wgrad_workspace_floats(int64_t N, int K, int Cin,
 TP3D_EXPORT int tp3d_sparse_wgrad_f32(const float *x, const float *dy, const int32_t *table, int64_t N, int64_t Nsrc, int K,
                                       int Cin, int Cout, float *dW, float *workspace, size_t workspace_floats, void *stream)
 {
-    if (N < 0 || Nsrc < 0 || K <= 0 || K > 27 || Cin <= 0 || Cout <= 0 || !dW) return TP3D_E_BADARG;
+    if (N < 0 || Nsrc < 0 || K <= 0 || K > SP_KMAX || Cin <= 0 || Cout <= 0 || !dW) return TP3D_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
     const int64_t NK = (int64_t)K * Cin * Cout;
     if (N == 0 || Nsrc == 0) return zero_async(dW, (size_t)NK * sizeof(float), s);
@@ -501,6 +644,74 @@ TP3D_EXPORT int tp3d_sparse_wgrad_f32(const float *x, const float *dy, const int
     }
     hipLaunchKernelGGL(sp_wgrad_kernel, dim3((unsigned)chunks, (unsigned)K, (unsigned)tiles), dim3(SP_BLOCK), 0, s, x, dy, table,
                        N, Nsrc, K, Cin, Cout, sp_wgrad_chunk_rows(N), out);
+    if (int rc = check_launch()) return rc;
+    if (chunks > 1) return tn_reduce_splits(workspace, chunks, NK, dW, s);
+    return TP3D_OK;
+}
+
+// ---- wide first layer: Cin <= 4, 27 < K <= 125 ----
+static size_t spw_fwd_lds(int K, int Cin, int Cout) { return (size_t)K * Cin * Cout * 4 + (size_t)(SP_BLOCK / 64) * 4 * SPW_HITS * 4; }
+
+static bool spw_shape_ok(int K, int Cin, int Cout)
+{
+    return K > 27 && K <= SP_KMAX && Cin > 0 && Cin <= SPW_MAX_CIN && Cout > 0 && Cout <= 65536;
+}
+
+TP3D_EXPORT int tp3d_sparse_conv_wide_serves(int K, int Cin, int Cout)
+{
+    return spw_shape_ok(K, Cin, Cout) && spw_fwd_lds(K, Cin, Cout) <= (size_t)SPW_LDS_MAX;
+}
+
+TP3D_EXPORT int tp3d_sparse_conv_wide_f32(const float *x, const int32_t *table, const float *W, int64_t Nout, int64_t Nsrc, int K,
+                                          int Cin, int Cout, float *y, void *stream)
+{
+    if (Nout < 0 || Nsrc < 0 || !tp3d_sparse_conv_wide_serves(K, Cin, Cout)) return TP3D_E_BADARG;
+    if (Nout == 0) return TP3D_OK;
+    if (!table || !W || !y || (Nsrc > 0 && !x)) return TP3D_E_BADARG;
+    if (Nout >= 0x7fffffff || Nsrc >= 0x7fffffff) return TP3D_E_TOOBIG;
+    int64_t blocks = (Nout + SPW_FWD_ROWS - 1) / SPW_FWD_ROWS;
+    if (blocks > SPW_FWD_MAX_BLOCKS) blocks = SPW_FWD_MAX_BLOCKS;
+    const size_t lds = spw_fwd_lds(K, Cin, Cout);
+    allow_large_dynamic_lds<&sp_conv_wide_kernel>(SPW_LDS_MAX);
+    hipLaunchKernelGGL(sp_conv_wide_kernel, dim3((unsigned)blocks), dim3(SP_BLOCK), lds, (hipStream_t)stream, x, table, W, Nout,
+                       Nsrc, K, Cin, Cout, y);
+    return check_launch();
+}
+
+TP3D_EXPORT int tp3d_sparse_wgrad_wide_chunks(int64_t N, int K, int Cin, int Cout)
+{
+    if (N <= 0 || N >= 0x7fffffff || !spw_shape_ok(K, Cin, Cout) || spw_wgrad_waves(K, Cin, Cout) < 1) return 0;
+    const int64_t rows = spw_wgrad_chunk_rows(N);
+    return (int)((N + rows - 1) / rows);
+}
+
+TP3D_EXPORT size_t tp3d_sparse_wgrad_wide_workspace_floats(int64_t N, int K, int Cin, int Cout)
+{
+    const int chunks = tp3d_sparse_wgrad_wide_chunks(N, K, Cin, Cout);
+    return chunks <= 1 ? 0 : (size_t)chunks * K * Cin * Cout;
+}
+
+TP3D_EXPORT int tp3d_sparse_wgrad_wide_f32(const float *x, const float *dy, const int32_t *table, int64_t N, int64_t Nsrc, int K,
+                                           int Cin, int Cout, float *dW, float *workspace, size_t workspace_floats, void *stream)
+{
+    if (N < 0 || Nsrc < 0 || !spw_shape_ok(K, Cin, Cout) || !dW) return TP3D_E_BADARG;
+    const int waves = spw_wgrad_waves(K, Cin, Cout);
+    if (waves < 1) return TP3D_E_BADARG;  // the accumulators of one wave do not fit the LDS: the generic kernel serves it
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t NK = (int64_t)K * Cin * Cout;
+    if (N == 0 || Nsrc == 0) return zero_async(dW, (size_t)NK * sizeof(float), s);
+    if (!x || !dy || !table) return TP3D_E_BADARG;
+    if (N >= 0x7fffffff || Nsrc >= 0x7fffffff) return TP3D_E_TOOBIG;
+    const int chunks = tp3d_sparse_wgrad_wide_chunks(N, K, Cin, Cout);
+    float *out = dW;
+    if (chunks > 1) {
+        if (!workspace || workspace_floats < (size_t)chunks * NK) return TP3D_E_BADARG;
+        out = workspace;
+    }
+    const size_t lds = (size_t)waves * ((size_t)NK * 4 + 2 * SPW_HITS * 4);
+    allow_large_dynamic_lds<&sp_wgrad_wide_kernel>(SPW_LDS_MAX);
+    hipLaunchKernelGGL(sp_wgrad_wide_kernel, dim3((unsigned)chunks), dim3(64 * waves), lds, s, x, dy, table, N, Nsrc, K, Cin, Cout,
+                       spw_wgrad_chunk_rows(N), out);
     if (int rc = check_launch()) return rc;
     if (chunks > 1) return tn_reduce_splits(workspace, chunks, NK, dW, s);
     return TP3D_OK;

@@ -12,8 +12,8 @@ device: fragment descriptors trained with a mined contrastive loss, evaluated by
   evaluate_pair                    the tracker's sequence for one fragment pair (registration_tracker.py:123-145)
   FragmentDescriptor               backbone -> FC_layer head (FragmentKPConv's layout) -> unit rows; "match" mode loss
 
-Not served: MS-SVConv (its configs open with a kernel_size 5 convolution), RANSAC (open3d), TEASER++, the Minkowski and
-patch models, and compute_loss_label's pytorch_metric_learning miners.
+MS-SVConv lives in ms_svconv.py.  Not served: RANSAC (open3d), TEASER++, the Minkowski and patch models, and
+compute_loss_label's pytorch_metric_learning miners.
 """
 import math
 

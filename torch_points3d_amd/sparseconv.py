@@ -25,6 +25,14 @@ from . import fused as _fused
 from .kpconv import _require_gpu
 from .kpconv_blocks import FastBatchNorm1d
 
+# Route of the first layer of a wide kernel (Cin <= 4, 27 < K <= 125: WideConv3d with kernel_size 5).  "wide": the
+# hit-compacting kernels (tp3d_sparse_conv_wide_f32, tp3d_sparse_wgrad_wide_f32) wherever they serve the shape; "generic":
+# the kernels every other layer takes; "auto": the wide kernels for the shape classes where tools/bench_ms_svconv.py
+# (profiles/ms_svconv_bench.json, MI355X) measured them faster than the generic route by more than the spread of its 30
+# samples: Cin = 1 (forward 0.099 vs 0.130 ms, weight gradient 0.23 vs 0.59 ms at Cout = 32).  At Cin = 4 the forward ties
+# (0.206 vs 0.204 ms) and the weight gradient loses (0.78 vs 0.59 ms); Cin = 2 and 3 are not measured: all generic.
+WIDE_ROUTE = "auto"
+
 COORD_LIMIT = 1 << 18  # |x|, |y|, |z| below this at tensor stride 1
 BATCH_LIMIT = 1 << 9   # batch index below this
 _BAD_RANGE, _BAD_DUP, _BAD_SPAN = 1, 2, 4
@@ -188,9 +196,21 @@ def cat(*args):
     return first._like(torch.cat([t.F for t in args], dim=1))
 
 
+def _wide_route(K, cin):
+    """True when the layer (K offsets, cin input channels) is one the wide kernels are meant for and WIDE_ROUTE asks for them"""
+    if WIDE_ROUTE not in ("auto", "wide", "generic"):
+        raise ValueError("sparseconv.WIDE_ROUTE must be 'auto', 'wide' or 'generic', not %r" % (WIDE_ROUTE,))
+    return K > 27 and (cin == 1 if WIDE_ROUTE == "auto" else (WIDE_ROUTE == "wide" and cin <= 4))
+
+
 def _conv_launch(x, table, W, n_out, K, cin, cout, transposed):
     dev = x.device
     y = torch.empty((n_out, cout), dtype=torch.float32, device=dev)
+    if not transposed and _wide_route(K, cin) and _lib.load().tp3d_sparse_conv_wide_serves(K, cin, cout):
+        with _lib.on_device(dev):
+            _lib.call("tp3d_sparse_conv_wide_f32", _lib.ptr(x), _lib.ptr(table), _lib.ptr(W), n_out, x.shape[0], K, cin, cout,
+                      _lib.ptr(y), _lib.stream_ptr(dev))
+        return y
     with _lib.on_device(dev):
         _lib.call("tp3d_sparse_conv_f32", _lib.ptr(x), _lib.ptr(table), _lib.ptr(W), n_out, x.shape[0], K, cin, cout,
                   int(transposed), _lib.ptr(y), _lib.stream_ptr(dev))
@@ -222,10 +242,13 @@ class _GatherConv(torch.autograd.Function):
             n = table_y.shape[0]
             dw = torch.empty_like(W)
             h = _lib.load()
-            floats = h.tp3d_sparse_wgrad_workspace_floats(n, K, cin, cout)
+            # (a shape the wide kernel declines -- its accumulators do not fit the LDS -- has no chunks: the generic kernel)
+            wide = _wide_route(K, cin) and h.tp3d_sparse_wgrad_wide_chunks(n, K, cin, cout) > 0
+            entry = "tp3d_sparse_wgrad_wide_f32" if wide else "tp3d_sparse_wgrad_f32"
+            floats = (h.tp3d_sparse_wgrad_wide_workspace_floats if wide else h.tp3d_sparse_wgrad_workspace_floats)(n, K, cin, cout)
             ws = _lib.workspace("sparse_wgrad", 4 * floats, dev) if floats else None
             with _lib.on_device(dev):
-                _lib.call("tp3d_sparse_wgrad_f32", _lib.ptr(x), _lib.ptr(dy), _lib.ptr(table_y), n, x.shape[0], K, cin, cout,
+                _lib.call(entry, _lib.ptr(x), _lib.ptr(dy), _lib.ptr(table_y), n, x.shape[0], K, cin, cout,
                           _lib.ptr(dw), _lib.ptr(ws), floats, _lib.stream_ptr(dev))
         return dx, dw, None, None
 
@@ -253,7 +276,8 @@ def _check_conv_args(kernel_size, stride, dilation):
     if dilation != 1:
         raise NotImplementedError("sparse convolution: dilation %r is not supported (only 1)" % (dilation,))
     if kernel_size not in (1, 2, 3):
-        raise NotImplementedError("sparse convolution: kernel_size %r is not supported (1, 2 or 3)" % (kernel_size,))
+        raise NotImplementedError("sparse convolution: kernel_size %r is not supported (1, 2 or 3; WideConv3d serves "
+                                  "kernel_size 5 at stride 1)" % (kernel_size,))
     if stride not in (1, 2):
         raise NotImplementedError("sparse convolution: stride %r is not supported (1 or 2)" % (stride,))
 
@@ -263,7 +287,7 @@ class Conv3d(nn.Module):
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, dilation=1, bias=False, transposed=False):
         super().__init__()
-        _check_conv_args(kernel_size, stride, dilation)
+        self._check_args(kernel_size, stride, dilation, transposed)
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.stride, self.dilation, self.transposed = kernel_size, stride, dilation, transposed
         K = kernel_size ** 3
@@ -271,6 +295,10 @@ class Conv3d(nn.Module):
         self.kernel = nn.Parameter(torch.zeros(*shape))
         self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
         self.reset_parameters()
+
+    @staticmethod
+    def _check_args(kernel_size, stride, dilation, transposed):
+        _check_conv_args(kernel_size, stride, dilation)
 
     def reset_parameters(self):
         # torchsparse 1.x: uniform(-std, std), std = 1 / sqrt(fan) with the fan of the side the kernel multiplies
@@ -322,6 +350,24 @@ class Conv3dTranspose(Conv3d):
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, dilation=1, bias=False, transpose=False):
         super().__init__(in_channels, out_channels, kernel_size=kernel_size, stride=stride, dilation=dilation, bias=bias,
                          transposed=True)
+
+
+class WideConv3d(Conv3d):
+    """Conv3d that also takes kernel_size 5: stride 1, dilation 1, not transposed (the first layer of MS-SVConv).  Same
+    parameter (`kernel` (k^3, Cin, Cout)) and initialisation; offsets {-2 .. 2} * tensor stride per axis, x slowest, z fastest
+    -- the continuation of the recalled torchsparse 1.x order, not verified against a checkpoint.  Up to 4 input
+    channels the layer takes the wide kernels (WIDE_ROUTE), else the generic ones."""
+
+    @staticmethod
+    def _check_args(kernel_size, stride, dilation, transposed):
+        if dilation != 1:
+            raise NotImplementedError("sparse convolution: dilation %r is not supported (only 1)" % (dilation,))
+        if kernel_size not in (3, 5):
+            raise NotImplementedError("WideConv3d: kernel_size %r is not supported (3 or 5)" % (kernel_size,))
+        if stride != 1:
+            raise NotImplementedError("WideConv3d: stride %r is not supported (only 1)" % (stride,))
+        if transposed:
+            raise NotImplementedError("WideConv3d: the transposed form is not supported")
 
 
 class _FeatureBatchNorm(nn.BatchNorm1d):
@@ -412,8 +458,14 @@ class ResNetDown(nn.Module):
         block = _BLOCKS[block]
         conv1_output = down_conv_nn[0] if stride > 1 else down_conv_nn[1]
         conv = self.CONVOLUTION
-        self.conv_in = (Seq().append(conv(in_channels=down_conv_nn[0], out_channels=conv1_output, kernel_size=kernel_size,
-                                          stride=stride, dilation=dilation))
+        conv_first = conv
+        if kernel_size > 3:  # (the blocks below are always kernel_size 3)
+            if conv is not Conv3d:
+                raise NotImplementedError("%s: kernel_size %r is not supported (a transposed convolution takes 2 or 3)"
+                                          % (type(self).__name__, kernel_size))
+            conv_first = WideConv3d
+        self.conv_in = (Seq().append(conv_first(in_channels=down_conv_nn[0], out_channels=conv1_output, kernel_size=kernel_size,
+                                                stride=stride, dilation=dilation))
                         .append(BatchNorm(conv1_output)).append(ReLU()))
         if N > 0:
             self.blocks = Seq()
@@ -483,6 +535,11 @@ class _BaseSparseConv3d(nn.Module):
         cfg = sparseconv3d_config(config, input_nc, in_feat, block) if isinstance(config, str) else config
         down, up = cfg["down_conv"], cfg.get("up_conv")
         n_down = len(down["down_conv_nn"])
+        # a stage list without `N` (conf/models/*/ms_svconv_base.yaml) takes ResNetDown's default of one block per stage;
+        # keys that ResNetDown has no use for (module_name, dimension, bn_momentum, ...) end in its **kwargs
+        down = dict(down, N=down.get("N", [1] * n_down))
+        if up is not None:
+            up = dict(up, N=up.get("N", [1] * len(up["up_conv_nn"])))
         for key in ("N", "kernel_size", "stride"):
             if len(down[key]) != n_down or (up is not None and len(up[key]) != len(up["up_conv_nn"])):
                 raise ValueError("sparseconv3d configuration %r: `%s` has not one entry per layer (the reference cannot build "

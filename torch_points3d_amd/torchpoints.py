@@ -860,6 +860,74 @@ def gather_rows(x, idx):
     return _GatherRows.apply(x, idx)
 
 
+_SCALE_FUSE_MODES = {"cat": 0, "max": 1, "mean": 2}
+
+
+def _ptr_array(tensors):
+    import ctypes
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+class _ScaleFuse(torch.autograd.Function):
+    """(mode, eps, want_scales, x_0 .. x_{S-1}) -> (out, xhat (S, N, C) or None); one launch each way (csrc/scale_fuse.hip)"""
+
+    @staticmethod
+    def forward(ctx, mode, eps, want_scales, *xs):
+        xs = [_f32(x.detach()) for x in xs]
+        S, (N, C), dev = len(xs), xs[0].shape, xs[0].device
+        out = torch.empty((N, S * C if mode == 0 else C), dtype=torch.float32, device=dev)
+        norm = torch.empty((N, S), dtype=torch.float32, device=dev)
+        xhat = torch.empty((S, N, C), dtype=torch.float32, device=dev) if want_scales and mode != 0 else None
+        arg = torch.empty((N, C), dtype=torch.uint8, device=dev) if mode == 1 else None
+        with _lib.on_device(dev):
+            _lib.call("tp3d_scale_fuse_fwd_f32", _ptr_array(xs), S, N, C, mode, float(eps), _lib.ptr(out), _lib.ptr(xhat),
+                      _lib.ptr(norm), _lib.ptr(arg), _lib.stream_ptr(dev))
+        ctx.save_for_backward(norm, arg, *xs)
+        ctx.mode, ctx.eps = mode, float(eps)
+        ctx.set_materialize_grads(False)
+        return out, xhat  # (xhat is None unless the scales of "max" / "mean" were asked for)
+
+    @staticmethod
+    def backward(ctx, gout, gxhat):
+        norm, arg = ctx.saved_tensors[:2]
+        xs = list(ctx.saved_tensors[2:])
+        S, (N, C), dev = len(xs), xs[0].shape, xs[0].device
+        if gout is None and gxhat is None:
+            return (None, None, None) + tuple(torch.zeros_like(x) for x in xs)
+        gout = None if gout is None else _f32(gout)
+        gxhat = None if gxhat is None else _f32(gxhat)
+        dxs = [torch.empty_like(x) for x in xs]
+        with _lib.on_device(dev):
+            _lib.call("tp3d_scale_fuse_bwd_f32", _ptr_array(xs), S, N, C, ctx.mode, ctx.eps, _lib.ptr(gout), _lib.ptr(gxhat),
+                      _lib.ptr(norm), _lib.ptr(arg), _ptr_array(dxs), _lib.stream_ptr(dev))
+        return (None, None, None) + tuple(dxs)
+
+
+def scale_fuse(xs, mode="cat", eps=1e-20, return_scales=False):
+    """The multi-scale head of MS-SVConv in one launch: xhat_s = x_s / (||x_s||_2 + eps) per row of each of the S <= 8
+    tensors xs[s] (N, C) fp32, then "cat": (N, S * C) with scale s in columns [s C, (s + 1) C); "max" / "mean" over the
+    scales: (N, C).  return_scales: also the list of the S normalised tensors (for "cat" column views of the output).
+    The backward is one launch of the exact gradient: max sends it to the winning scale (ties to the lowest scale index, as
+    torch's max(0) on the CPU); an all-zero row gives 0 forward and g / eps backward (torch's result for the same
+    formula).  Norms and dot products are fixed-order lane reductions: no atomics, repeats are bit-equal."""
+    xs = list(xs)
+    if mode not in _SCALE_FUSE_MODES:
+        raise ValueError("scale_fuse: mode %r is not one of 'cat', 'max', 'mean'" % (mode,))
+    if not 1 <= len(xs) <= 8:
+        raise ValueError("scale_fuse takes 1 to 8 scales, got %d" % len(xs))
+    _dev(*xs)
+    for x in xs:
+        if x.dim() != 2 or x.shape != xs[0].shape or x.shape[1] < 1:
+            raise ValueError("scale_fuse: every scale must be (N, C) with one N and one C >= 1")
+    out, xhat = _ScaleFuse.apply(_SCALE_FUSE_MODES[mode], eps, bool(return_scales), *xs)
+    if not return_scales:
+        return out
+    C = xs[0].shape[1]
+    if mode == "cat":
+        return out, [out[:, s * C:(s + 1) * C] for s in range(len(xs))]
+    return out, list(xhat.unbind(0))
+
+
 def fgr(xyz, xyz_target, mu_init=1.0, num_iter=20):
     """Fast Global Registration (utils/registration.py:83-103) of the correspondences xyz[i] <-> xyz_target[i], both (N, 3):
     the (4, 4) fp32 pose T with xyz_target ~ xyz @ T[:3, :3].T + T[:3, 3].  Two launches per iteration (the normal equations
