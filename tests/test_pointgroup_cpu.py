@@ -129,3 +129,118 @@ def test_scene_generator_keeps_its_promises():
     # (label ascending, lowest member ascending) is the list order
     keys = [(int(labels[c[0]]), c[0]) for c in ref]
     assert keys == sorted(keys)
+
+
+# ---- the edge generators of test_gpu_region_grow_edges.py, held to their own guarantees without a GPU -----------------
+# Every generator asserts its margins (and, where it has them, its intended cells) when called; here the host walk, the
+# float64 components and the literal expectation are shown to agree, so that a failure on the GPU points at the kernel.
+def _host(s, **kw):
+    from test_gpu_region_grow import host
+    return host(s, **kw)
+
+
+def _components(s, ignore=pgu.IGNORE, radius=pgu.RADIUS, min_cluster_size=pgu.MIN_CLUSTER_SIZE):
+    return pgu.components_reference(s["pos"], s["labels"], s["batch"], list(ignore), radius, min_cluster_size)
+
+
+@pytest.mark.parametrize("which", sorted(pgu.SHIFTS))
+def test_edges_shifted_scenes_keep_the_clusters(which):
+    s, base = pgu.scene_shifted(which), pgu.scene()
+    assert torch.equal(s["labels"], base["labels"]) and torch.equal(s["batch"], base["batch"])
+    shift = torch.tensor(pgu.SHIFTS[which], dtype=torch.float64) * pgu.H
+    assert float((s["pos"].double() - base["pos"].double() - shift).abs().max()) <= pgu.H / 64 + 1e-12  # at most the jitter
+    assert _host(s) == pgu.scene_reference() == _components(s)
+
+
+def test_edges_far_point_is_beyond_the_coordinate_limit():
+    s = pgu.scene_with_far_point(1e6)
+    assert int(pgu.cells_fp32(s["pos"][-1:].numpy(), pgu.RADIUS)[0, 0]) > 1 << 24
+    assert _host(s) == pgu.scene_reference() == _components(s)  # the far single is dropped
+
+
+@pytest.mark.parametrize("swap", [False, True])
+def test_edges_twenty_six_pairs(swap):
+    s = pgu.pairs26(swap)  # asserts the cells of every pair
+    want = [[2 * i, 2 * i + 1] for i in range(26)]
+    assert s["want"] == want == _host(s, min_cluster_size=2) == _components(s, min_cluster_size=2)
+    low_end_first = s["pos"][0::2, 0] < s["pos"][1::2, 0]  # pairs across +x: which end is the lower index
+    dx = torch.tensor([d[0] for d in pgu.DIRS26 + pgu.DIRS26])
+    assert bool((low_end_first[dx == 1] != swap).all()) and bool((low_end_first[dx == -1] == swap).all())
+
+
+@pytest.mark.parametrize("extra", [None, "label4095", "label-1", "cloud1024", "ignored"])
+def test_edges_key_field_pairs(extra):
+    s = pgu.pairs26_fields(extra)
+    assert bool((s["batch"][1:] >= s["batch"][:-1]).all())
+    assert sorted(s["batch"].unique().tolist())[:3] == list(pgu.FIELD_CLOUDS)
+    kw = dict(ignore_labels=s["ignore"], min_cluster_size=2)
+    assert s["want"] == _host(s, **kw) == _components(s, s["ignore"], min_cluster_size=2)
+    if extra is not None:  # the extra points are there, and are singles: min_cluster_size 1 shows them
+        assert len(_host(s, ignore_labels=(), min_cluster_size=1)) == 26 + 52 + (2 if extra == "ignored" else 1)
+
+
+@pytest.mark.parametrize("axis", [0, 1, 2])
+@pytest.mark.parametrize("k", [pgu.CELL_MAX, pgu.CELL_MAX + 1])
+def test_edges_span_limit(axis, k):
+    s = pgu.span_limit(axis, k)  # asserts the intended cells
+    assert pgu.CELL_MAX == (1 << 14) - 3 and int(s["cells"][:, axis].max() - s["cells"][:, axis].min()) == k
+    assert s["want"] == _host(s, min_cluster_size=3) == _components(s, min_cluster_size=3)
+
+
+@pytest.mark.parametrize("count", [63, 64, 65, 128, 129])
+def test_edges_piles(count):
+    from test_gpu_region_grow import pile
+    s = pile(count)
+    pgu.check_margins(s["pos"], s["batch"], pgu.RADIUS, 300)
+    want = [list(range(1, count + 1))]
+    assert want == _host(s, nsample=300) == _components(s)
+    s = pgu.pile3(count)
+    assert s["want"] == [list(range(1, 3 * count + 1))] == _components(s)
+    if 3 * count <= 300:
+        pgu.check_margins(s["pos"], s["batch"], pgu.RADIUS, 300)
+        assert s["want"] == _host(s, nsample=300)
+
+
+def test_edges_strict_pairs():
+    s = pgu.strict_pairs()  # asserts d2 == r2 and d2 < r2 in fp32
+    assert s["want"] == [[0], [1], [2, 3]] == _host(s, radius=pgu.STRICT_RADIUS, min_cluster_size=1)
+    # (no float64 components here: cKDTree's ball is closed and joins the pair on the radius)
+
+
+@pytest.mark.parametrize("runs", [1, 1023, 1024, 1025, 2049])
+def test_edges_line_of_singles(runs):
+    s = pgu.line_of_singles(runs)
+    assert s["want"] == [[i] for i in range(runs)] == _host(s, min_cluster_size=1) == _components(s, min_cluster_size=1)
+    assert int(pgu.cells_fp32(s["pos"].numpy(), pgu.RADIUS)[:, 0].max()) == 3 * (runs - 1) <= pgu.CELL_MAX
+
+
+@pytest.mark.parametrize("ignored", [0, 100])
+def test_edges_alternating_runs(ignored):
+    s = pgu.alternating_runs(2049, ignored)
+    assert int((s["labels"] == 0).sum()) == ignored and s["pos"].shape[0] == 1025 * 2 + 1024 + ignored
+    assert len(s["want"]) == 1025 and s["want"] == _host(s, min_cluster_size=2) == _components(s, min_cluster_size=2)
+    # at min_cluster_size 1 the runs alternate pair, single, pair, ... in list order
+    sizes = [len(c) for c in _components(s, min_cluster_size=1)]
+    assert sizes == [2, 1] * 1024 + [2]
+
+
+@pytest.mark.parametrize("order", ["ascending", "descending", "bitrev"])
+def test_edges_snake_chain(order):
+    s = pgu.snake_chain(order)
+    n = pgu.SNAKE_ROW * pgu.SNAKE_ROWS + pgu.SNAKE_ROWS
+    assert s["want"] == [list(range(n))] == _host(s) == _components(s)
+    idx = s["index"]
+    step = np.abs(np.diff(idx))
+    if order == "bitrev":  # neighbours on the path are far apart in index, every second step by about half the range
+        assert sorted(idx.tolist()) == list(range(n)) and np.median(step) > n // 4
+    else:
+        assert np.all(step == 1) and idx[0] == (0 if order == "ascending" else n - 1)
+    d = np.linalg.norm(np.diff(s["pos"].numpy()[idx].astype(np.float64), axis=0), axis=1)
+    assert d.max() < pgu.RADIUS  # consecutive positions on the path are linked: a chain
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_edges_scene_permutations(seed):
+    s, base = pgu.scene_permuted(seed), pgu.scene()
+    assert not np.array_equal(s["perm"], np.arange(len(s["perm"]))) and torch.equal(s["pos"], base["pos"][s["perm"]])
+    assert pgu.map_back(_host(s), s) == pgu.scene_reference()

@@ -225,7 +225,8 @@ __global__ __launch_bounds__(RG_BLOCK) void rg_hook_kernel(const unsigned long l
             const int id = __float_as_int(pt.w);
             // the graph is undirected: the edge (i, id) is also seen from id, so the higher end unites
             const bool link = hit && id < i;
-            if (__ballot(link) == 0) continue;
+            const unsigned long long links = __ballot(link);
+            if (links == 0) continue;
             int first;
             const int r = rg_find(parent, link ? id : i, first);
             int m = r;
@@ -239,6 +240,9 @@ __global__ __launch_bounds__(RG_BLOCK) void rg_hook_kernel(const unsigned long l
                 if (lane == leader) rg_hook(parent, rl, m);
                 pending &= ~__ballot(r == rl);
             }
+            // a lane without a link walks from the point itself; when all 64 lanes hold one (64 lower-indexed
+            // neighbours in one stretch of a run) none has, and the point is united here
+            if (links == ~0ull && lane == 0) rg_hook(parent, i, m);
             // shorten the paths: m is now in the set of every lane's point and no larger than its root was; a root is
             // the lowest id of its set, so this never lowers a root's own entry
             if ((link || lane == 0) && first > m) atomicMin(parent + (link ? id : i), m);
