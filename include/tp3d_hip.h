@@ -719,6 +719,37 @@ int tp3d_fgr_accumulate_f32(const float *xyz, const float *xyz_target, int64_t N
                             size_t workspace_bytes, void *stream);
 int tp3d_fgr_solve(int64_t N, int iter, double mu_init, float *T, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Per-cloud row kernels of PointNet (csrc/segment_rows.hip)
+ *                                  [core/common_modules/spatial_transform.py:44-49, modules/PointNet/modules.py:33-35, :108]
+ *   seg (B + 1) int64: the row offsets of the clouds, ascending, seg[0] = 0, seg[B] = N, empty clouds allowed; fp32 data;
+ *   row strides (ld*) in floats.  No float atomics, nothing of size N * k * k is written, repeats are bit-equal.
+ *   tp3d_segment_transform_f32: x (N, ldx), T (B, k, k) -> out (N, ldo); for row i of cloud b
+ *     out[i, c] = sum_j x[i, j] * T[b, j, c] (transpose != 0: T[b, c, j]) for c < k, one fp32 fma chain, j ascending;
+ *     out[i, c] = x[i, c] for k <= c < C; 0 for C <= c < ldo.  1 <= k <= 64, k <= C <= ldx, ldo (else TP3D_E_BADARG).
+ *     With T[b] the identity out[:, :C] is x bit for bit (up to the sign of a zero); transpose = 1 on dy is the input
+ *     gradient.  out must not overlap x.  A workgroup serves tp3d_segment_tile_rows() consecutive rows.
+ *   tp3d_segment_transform_wgrad_f32: dT (B, k, k): dT[b, j, c] = sum over the rows i of cloud b of x[i, j] * dy[i, c].
+ *     Every cloud is cut into chunks of tp3d_segment_sum_chunk() rows from its first row; a chunk is summed in ascending
+ *     row order (one fma chain per entry), a cloud's chunks are added in ascending order; an empty cloud gives zeros.
+ *     workspace: tp3d_segment_transform_wgrad_workspace_bytes(N, B, k).
+ *   tp3d_segment_bcast_cat_f32: x (N, ldx) or NULL with C1 = 0, g (B, ldg) -> out (N, ldo):
+ *     out[i] = [ x[i, 0:C1] | g[b(i), 0:C2] | 0 .. ldo ).
+ *   tp3d_segment_sum_f32: out (B, C): out[b, c] = scale[b] * sum over the rows i of cloud b of rows[i, col0 + c], rows
+ *     (N, ld), scale (B) or NULL (= 1); the chunked order of the weight gradient.
+ *     workspace: tp3d_segment_sum_workspace_bytes(N, B, C). */
+int tp3d_segment_tile_rows(void);
+int tp3d_segment_sum_chunk(void);
+int tp3d_segment_transform_f32(const float *x, const float *T, const int64_t *seg, int64_t N, int64_t B, int k, int C, int ldx,
+                               int ldo, int transpose, float *out, void *stream);
+size_t tp3d_segment_transform_wgrad_workspace_bytes(int64_t N, int64_t B, int k);
+int tp3d_segment_transform_wgrad_f32(const float *x, const float *dy, const int64_t *seg, int64_t N, int64_t B, int k, int ldx,
+                                     int lddy, float *dT, void *workspace, size_t workspace_bytes, void *stream);
+int tp3d_segment_bcast_cat_f32(const float *x, const float *g, const int64_t *seg, int64_t N, int64_t B, int C1, int C2, int ldx,
+                               int ldg, int ldo, float *out, void *stream);
+size_t tp3d_segment_sum_workspace_bytes(int64_t N, int64_t B, int C);
+int tp3d_segment_sum_f32(const float *rows, const int64_t *seg, const float *scale, int64_t N, int64_t B, int col0, int C, int ld,
+                         float *out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* =====================================================================================================
  * Launch plans (host arithmetic only, no device work): what an entry point WILL do for given sizes -- how it
  * splits the rows, how many partial rows it writes, how it carves its workspace.  tests/test_plans_cpu.py sweeps

@@ -100,6 +100,10 @@ SIGNATURES = {
     "tp3d_feature_nn_f32": [_p, _p, _p, _p, _l, _l, _i, _f, _p, _p, _p, ctypes.c_size_t, _p],
     "tp3d_fgr_accumulate_f32": [_p, _p, _l, _i, _p, ctypes.c_size_t, _p],
     "tp3d_fgr_solve": [_l, _i, ctypes.c_double, _p, _p, ctypes.c_size_t, _p],
+    "tp3d_segment_transform_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _i, _i, _p, _p],
+    "tp3d_segment_transform_wgrad_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
+    "tp3d_segment_bcast_cat_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _i, _i, _p, _p],
+    "tp3d_segment_sum_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
     # launch plans (host arithmetic; the last argument is a HOST int64 array)
     "tp3d_gemm_tn_plan": [_l, _i, _i, _p],
     "tp3d_gemm_tn_x3_plan": [_l, _i, _i, _p],
@@ -143,6 +147,10 @@ MISC = {
     "tp3d_region_grow_workspace_bytes": (_z, [_l]),
     "tp3d_feature_nn_workspace_bytes": (_z, [_l, _l, _i]),
     "tp3d_fgr_workspace_bytes": (_z, [_l]),
+    "tp3d_segment_tile_rows": (_i, []),
+    "tp3d_segment_sum_chunk": (_i, []),
+    "tp3d_segment_transform_wgrad_workspace_bytes": (_z, [_l, _l, _i]),
+    "tp3d_segment_sum_workspace_bytes": (_z, [_l, _l, _i]),
 }
 ABI_VERSION = 39
 

@@ -951,3 +951,193 @@ def fgr(xyz, xyz_target, mu_init=1.0, num_iter=20):
             _lib.call("tp3d_fgr_accumulate_f32", _lib.ptr(xyz), _lib.ptr(xyz_target), N, i, _lib.ptr(ws), nbytes, stream)
             _lib.call("tp3d_fgr_solve", N, i, float(mu_init), _lib.ptr(T), _lib.ptr(ws), nbytes, stream)
     return T
+
+
+# ------------------------------------------------------------------------------------------------ PointNet's per-cloud rows
+SEG_TILE_ROWS = 64   # rows a workgroup of tp3d_segment_transform_f32 serves (SEG_TILE_ROWS of csrc/segment_rows.hip)
+SEG_SUM_CHUNK = 128  # chunk length of the fixed-order sums (SEG_SUM_CHUNK of csrc/segment_rows.hip)
+SEG_MAX_K = 64       # largest transform the kernels hold in LDS
+
+
+def _rows_ld(t):
+    """(fp32 rows usable in place, row stride in floats): a 2-D tensor whose rows are dense is taken as it is, whatever
+    the distance between its rows; anything else is made contiguous."""
+    t = t.detach()
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.dim() == 2 and t.shape[0] > 0 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+        return t, t.stride(0)
+    t = t.contiguous()
+    return t, max(t.shape[1], 1)
+
+
+def _cloud_rows(batch, seg, N):
+    """(seg (B + 1,) int64, B) from explicit offsets or from a sorted batch vector (the cached `_segments`)"""
+    if seg is not None:
+        if seg.dim() != 1 or seg.numel() < 1:
+            raise ValueError("seg must be (B + 1,)")
+        return _i64(seg), seg.numel() - 1
+    if batch is None:
+        raise ValueError("either batch or seg is needed")
+    if batch.dim() != 1 or (N is not None and batch.numel() != N):
+        raise ValueError("batch must have one entry per row")
+    seg, B, _ = _segments(_i64(batch))
+    return seg, B
+
+
+def _seg_transform(xf, ldx, T, seg, C, transpose):
+    dev = xf.device
+    N, (B, k) = xf.shape[0], T.shape[:2]
+    out = torch.empty((N, C), dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_segment_transform_f32", _lib.ptr(xf), _lib.ptr(T), _lib.ptr(seg), N, B, k, C, ldx, C, transpose,
+                  _lib.ptr(out), _lib.stream_ptr(dev))
+    return out
+
+
+def _seg_sum(rf, ld, seg, B, col0, C, scale):
+    dev = rf.device
+    N = rf.shape[0]
+    out = torch.empty((B, C), dtype=torch.float32, device=dev)
+    if B == 0 or C == 0:
+        return out
+    nbytes = _lib.load().tp3d_segment_sum_workspace_bytes(N, B, C)
+    ws = _lib.workspace("segment", nbytes, dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_segment_sum_f32", _lib.ptr(rf), _lib.ptr(seg), _lib.ptr(scale), N, B, col0, C, ld, _lib.ptr(out),
+                  _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+    return out
+
+
+def _seg_bcast_cat(xf, ldx, gf, ldg, seg, N, B, C1, C2):
+    dev = gf.device
+    out = torch.empty((N, C1 + C2), dtype=torch.float32, device=dev)
+    if N and C1 + C2:
+        with _lib.on_device(dev):
+            _lib.call("tp3d_segment_bcast_cat_f32", _lib.ptr(xf), _lib.ptr(gf), _lib.ptr(seg), N, B, C1, C2, ldx, ldg,
+                      C1 + C2, _lib.ptr(out), _lib.stream_ptr(dev))
+    return out
+
+
+class _SegmentTransform(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, trans, seg):
+        xf, ldx = _rows_ld(x)
+        T = _f32(trans)
+        ctx.save_for_backward(xf, T, seg)
+        ctx.ldx = ldx
+        return _seg_transform(xf, ldx, T, seg, xf.shape[1], 0)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xf, T, seg = ctx.saved_tensors
+        dev = dy.device
+        dyf, ldd = _rows_ld(dy)
+        N, (B, k) = xf.shape[0], T.shape[:2]
+        dx = dT = None
+        if ctx.needs_input_grad[0]:
+            dx = _seg_transform(dyf, ldd, T, seg, xf.shape[1], 1)
+        if ctx.needs_input_grad[1]:
+            dT = torch.empty((B, k, k), dtype=torch.float32, device=dev)
+            nbytes = _lib.load().tp3d_segment_transform_wgrad_workspace_bytes(N, B, k)
+            ws = _lib.workspace("segment", nbytes, dev)
+            with _lib.on_device(dev):
+                _lib.call("tp3d_segment_transform_wgrad_f32", _lib.ptr(xf), _lib.ptr(dyf), _lib.ptr(seg), N, B, k, ctx.ldx,
+                          ldd, _lib.ptr(dT), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+        return dx, dT, None
+
+
+def segment_transform(x, trans, batch=None, seg=None):
+    """The spatial transformer's application (core/common_modules/spatial_transform.py:44-54) without `trans[batch]`:
+    out[i] = [ x[i, :k] @ trans[b(i)] | x[i, k:] ] for x (N, C) and trans (B, k, k), k <= C, k <= 64; the clouds are the
+    runs of a sorted `batch` (N,) or the row offsets `seg` (B + 1,).  x (B, n, C), the dense layout, is served as B
+    clouds of n rows.  Differentiable wrt x and trans; no float atomics, repeats are bit-equal."""
+    if trans.dim() != 3 or trans.shape[1] != trans.shape[2] or x.dim() not in (2, 3):
+        raise ValueError("x must be (N, C) or (B, n, C) and trans (B, k, k)")
+    k = trans.shape[1]
+    if k > SEG_MAX_K:
+        raise NotImplementedError("segment_transform holds the k x k matrix of a cloud in LDS and serves k <= %d, got k = "
+                                  "%d" % (SEG_MAX_K, k))
+    if k < 1 or x.shape[-1] < k:
+        raise ValueError("x needs at least k = %d columns" % k)
+    dev = _dev(x, trans, batch, seg)
+    if x.dim() == 3:
+        if batch is not None or seg is not None:
+            raise ValueError("a dense x (B, n, C) carries its own clouds")
+        Bd, n, C = x.shape
+        seg = torch.arange(Bd + 1, dtype=torch.int64, device=dev) * n
+        rows = x.reshape(Bd * n, C)
+    else:
+        rows = x
+        seg, _ = _cloud_rows(batch, seg, x.shape[0])
+    if seg.numel() - 1 != trans.shape[0]:
+        raise ValueError("trans holds %d matrices for %d clouds" % (trans.shape[0], seg.numel() - 1))
+    out = _SegmentTransform.apply(rows, trans, seg)
+    return out.view(x.shape) if x.dim() == 3 else out
+
+
+class _SegmentBcastCat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, g, seg, N):
+        gf, ldg = _rows_ld(g)
+        xf, ldx = (None, 1) if x is None else _rows_ld(x)
+        C1 = 0 if x is None else xf.shape[1]
+        ctx.save_for_backward(seg)
+        ctx.cfg = (C1, gf.shape[1], gf.shape[0])
+        return _seg_bcast_cat(xf, max(ldx, C1), gf, ldg, seg, N, gf.shape[0], C1, gf.shape[1])
+
+    @staticmethod
+    def backward(ctx, dout):
+        (seg,) = ctx.saved_tensors
+        C1, C2, B = ctx.cfg
+        dx = dg = None
+        if C1 and ctx.needs_input_grad[0]:
+            dx = dout[:, :C1]
+        if ctx.needs_input_grad[1]:
+            df, ldd = _rows_ld(dout)
+            dg = _seg_sum(df, ldd, seg, B, C1, C2, None)
+        return dx, dg, None, None
+
+
+def segment_broadcast_cat(x, g, batch=None, seg=None):
+    """cat([x, g[batch]], 1) in one pass (modules/PointNet/modules.py:33-35, :108): x (N, C1) or None, g (B, C2), the
+    clouds as in `segment_transform` -> (N, C1 + C2).  Differentiable wrt both: dx is a view of the incoming gradient, dg
+    the per-cloud sum in the fixed chunked order (no float atomics)."""
+    dev = _dev(g, x, batch, seg)
+    if g.dim() != 2 or (x is not None and x.dim() != 2):
+        raise ValueError("x must be (N, C1) or None and g (B, C2)")
+    N = x.shape[0] if x is not None else (batch.numel() if batch is not None else None)
+    seg, B = _cloud_rows(batch, seg, N)
+    if B != g.shape[0]:
+        raise ValueError("g holds %d rows for %d clouds" % (g.shape[0], B))
+    if N is None:
+        N = int(seg[-1])  # (x is None and only seg is known: the one host read)
+    return _SegmentBcastCat.apply(x, g, seg.to(dev), N)
+
+
+class _SegmentMeanRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rows, seg):
+        rf, ld = _rows_ld(rows)
+        B = seg.numel() - 1
+        scale = (1.0 / (seg[1:] - seg[:-1]).clamp(min=1).float()).contiguous()
+        ctx.save_for_backward(seg, scale)
+        ctx.shape = tuple(rf.shape)
+        return _seg_sum(rf, ld, seg, B, 0, rf.shape[1], scale)
+
+    @staticmethod
+    def backward(ctx, dout):
+        seg, scale = ctx.saved_tensors
+        N, C = ctx.shape
+        gs = (dout.float() * scale[:, None]).contiguous()
+        return _seg_bcast_cat(None, 1, gs, max(C, 1), seg, N, gs.shape[0], 0, C), None
+
+
+def segment_mean_rows(rows, seg):
+    """global_mean_pool over consecutive rows: out (B, C) = the mean of rows[seg[b] : seg[b + 1]], summed in the fixed
+    chunked order of csrc/segment_rows.hip (chunks of SEG_SUM_CHUNK rows in ascending order, then the chunks in ascending
+    order); an empty cloud gives zeros.  Differentiable wrt rows."""
+    _dev(rows, seg)
+    if rows.dim() != 2 or rows.shape[1] < 1 or seg.dim() != 1 or seg.numel() < 1:
+        raise ValueError("rows must be (N, C) and seg (B + 1,)")
+    return _SegmentMeanRows.apply(rows, _i64(seg))
