@@ -588,6 +588,10 @@ int tp3d_rsconv_msgmax_bwd_f32(const float *dout, const int64_t *arg, const floa
  *   tp3d_sparse_set_build_i32: ts = the tensor stride of `coords` (the range rule above).  down == 0: the set of `coords` themselves, rows in the caller's order (keys_out, rows_out: N).
  *     down > 0: the distinct floor(c / down) * down per axis (batch kept), ascending (batch, x, y, z): keys_out, rows_out
  *     (= iota) and coords_out (., 4) sized for N rows, meta[8] of them written.
+ *   tp3d_sparse_set_build_clouds_i32: the same with the caller's exclusive bound on the batch index, 1 <= cloud_limit <=
+ *     tp3d_sparse_cloud_limit_max() = 2^24 (else TP3D_E_BADARG), in place of 2^9: a sparse tensor with one cloud per
+ *     cluster.  Flag 4 still guards the key: extents * (highest batch + 1) must stay below 4e18.  Kernel maps and the
+ *     products read the batch through the key only and take any such set.
  *   tp3d_sparse_kmap_i32: table (Nq, ksize^3) int32 = the row of the set's voxel at qcoords[q] + sign * offset_k * step, -1
  *     where absent; offsets {-(k / 2) .. k / 2} (ksize 3 or 5), {0, 1} (ksize 2), {0} (ksize 1) per axis, x slowest, z
  *     fastest.  The convolution and weight gradient take K <= 125.
@@ -609,6 +613,10 @@ int tp3d_rsconv_msgmax_bwd_f32(const float *dout, const int64_t *arg, const floa
 size_t tp3d_sparse_workspace_bytes(int64_t N);
 int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int ts, int down, int64_t *keys_out, int32_t *rows_out,
                               int32_t *coords_out, int32_t *meta, void *workspace, size_t workspace_bytes, void *stream);
+int tp3d_sparse_cloud_limit_max(void);
+int tp3d_sparse_set_build_clouds_i32(const int32_t *coords, int64_t N, int ts, int down, int cloud_limit, int64_t *keys_out,
+                                     int32_t *rows_out, int32_t *coords_out, int32_t *meta, void *workspace,
+                                     size_t workspace_bytes, void *stream);
 int tp3d_sparse_kmap_i32(const int32_t *qcoords, int64_t Nq, int ksize, int step, int sign, const int64_t *keys,
                          const int32_t *rows, const int32_t *meta, int64_t Ns, int32_t *table, void *stream);
 int tp3d_sparse_kmap_mirror_i32(const int32_t *forward, int64_t N, int K, int32_t *inverse, void *stream);
@@ -671,7 +679,25 @@ int tp3d_pv_gather_f32(const float *src, const int32_t *table, const float *w, c
 int tp3d_pv_runsum_f32(const float *src, const int32_t *start, const int32_t *order, const float *w, const float *scale,
                        int64_t Nv, int K, int64_t Nsrc, int C, float *out, void *stream);
 
-/* Region growing of PointGroup (csrc/region_grow.hip)            [models/panoptic/pointgroup.py:98-121, region_grow]
+/* Cluster voxel mean of PointGroup's sparse scorers (csrc/cluster_voxel.hip)   [models/panoptic/pointgroup.py:123-141]
+ *   The clusters are a CSR over member slots: slot e holds the point members[e] (E int64).  Every slot belongs to one
+ *   voxel: voxel v owns the slots order[vstart[v] .. vstart[v + 1]) (int64, ascending slot: tp3d_voxel_cluster_f32 over
+ *   the slots), and slot_voxel[e] (E int64) names it.  x (N, ldx) fp32 are the rows of the points, C <= ldx.
+ *   tp3d_cluster_voxel_mean_fwd_f32: out (V, C): out[v] = (sum over the voxel's slots e, ascending, of x[members[e]]) / n_v.
+ *     x is read through voxel -> slot -> point; no (E, C) rows are written.
+ *   tp3d_cluster_voxel_mean_bwd_f32: dx (N, C) OVERWRITTEN: dx[p] = sum over the slots e with members[e] == p, ascending e,
+ *     of dout[slot_voxel[e]] / n_voxel; exact zeros for a point in no slot.  dout (V, C) dense.  pstart (N + 1), porder (E)
+ *     int32: the point -> slots index, porder[pstart[p] .. pstart[p + 1]) = the slots of p ascending -- tp3d_pv_invert_i32
+ *     of `members` with K = 1 and Nv = N.
+ *   Both: a run of more than 64 slots is summed in 16 contiguous pieces of ceil(n / 16) slots, each ascending, the pieces
+ *   added in order (the association of tp3d_pv_runsum_f32); an index outside its range counts as absent.  Lanes run across
+ *   channels, float4 where C % 4 == 0 and every row is 16-byte aligned.  No float atomics: repeats are bit-equal. */
+int tp3d_cluster_voxel_mean_fwd_f32(const float *x, int ldx, const int64_t *members, const int64_t *order, const int64_t *vstart,
+                                    int64_t N, int64_t E, int64_t V, int C, float *out, void *stream);
+int tp3d_cluster_voxel_mean_bwd_f32(const float *dout, const int64_t *slot_voxel, const int64_t *vstart, const int32_t *pstart,
+                                    const int32_t *porder, int64_t N, int64_t E, int64_t V, int C, float *dx, void *stream);
+
+/* Region growing of PointGroup (csrc/region_grow.hip)           [models/panoptic/pointgroup.py:98-121, region_grow]
  *   The connected components of the graph that joins points i, j when labels[i] == labels[j], batch[i] == batch[j], the
  *   label is not one of ignore[0 .. n_ignore) and (dx*dx + dy*dy) + dz*dz < radius * radius in fp32 -- the membership
  *   test of tp3d_ball_query_partial_dense_f32, uncapped.  pos (N,3), labels (N), batch (N, ascending); ignore is DEVICE

@@ -83,6 +83,7 @@ SIGNATURES = {
     "tp3d_rsconv_msgmax_fwd_f32": [_p, _i, _p, _i, _p, _p, _l, _l, _l, _i, _p, _p, _p],
     "tp3d_rsconv_msgmax_bwd_f32": [_p, _p, _p, _i, _p, _i, _p, _p, _l, _l, _l, _i, _p, _p, _p],
     "tp3d_sparse_set_build_i32": [_p, _l, _i, _i, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
+    "tp3d_sparse_set_build_clouds_i32": [_p, _l, _i, _i, _i, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
     "tp3d_sparse_kmap_i32": [_p, _l, _i, _i, _i, _p, _p, _p, _l, _p, _p],
     "tp3d_sparse_kmap_mirror_i32": [_p, _l, _i, _p, _p],
     "tp3d_sparse_conv_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _i, _p, _p],
@@ -96,6 +97,8 @@ SIGNATURES = {
     "tp3d_pv_invert_i32": [_p, _l, _i, _l, _p, _p, _p, ctypes.c_size_t, _p],
     "tp3d_pv_gather_f32": [_p, _p, _p, _p, _l, _i, _l, _i, _p, _p],
     "tp3d_pv_runsum_f32": [_p, _p, _p, _p, _p, _l, _i, _l, _i, _p, _p],
+    "tp3d_cluster_voxel_mean_fwd_f32": [_p, _i, _p, _p, _p, _l, _l, _l, _i, _p, _p],
+    "tp3d_cluster_voxel_mean_bwd_f32": [_p, _p, _p, _p, _p, _l, _l, _l, _i, _p, _p],
     "tp3d_region_grow_f32": [_p, _p, _p, _l, _p, _i, _f, _l, _p, _p, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
     "tp3d_feature_nn_f32": [_p, _p, _p, _p, _l, _l, _i, _f, _p, _p, _p, ctypes.c_size_t, _p],
     "tp3d_fgr_accumulate_f32": [_p, _p, _l, _i, _p, ctypes.c_size_t, _p],
@@ -138,6 +141,7 @@ MISC = {
     "tp3d_voxel_workspace_bytes": (_z, [_l]),
     "tp3d_ball_query_workspace_bytes": (_z, [_i, _l, _i]),
     "tp3d_sparse_workspace_bytes": (_z, [_l]),
+    "tp3d_sparse_cloud_limit_max": (_i, []),
     "tp3d_sparse_wgrad_chunks": (_i, [_l, _i, _i, _i]),
     "tp3d_sparse_wgrad_workspace_floats": (_z, [_l, _i, _i, _i]),
     "tp3d_sparse_conv_wide_serves": (_i, [_i, _i, _i]),

@@ -18,7 +18,8 @@ namespace tp3d {
 
 constexpr int SP_BLOCK = SK_BLOCK;
 constexpr int SP_COORD_LIMIT = 1 << 18;  // |coord| below this at tensor stride 1
-constexpr int SP_BATCH_LIMIT = 1 << 9;   // batch below this
+constexpr int SP_BATCH_LIMIT = 1 << 9;   // batch below this (tp3d_sparse_set_build_i32)
+constexpr int SP_CLOUD_LIMIT_MAX = 1 << 24;  // largest bound tp3d_sparse_set_build_clouds_i32 takes
 constexpr int SP_META = 16;
 constexpr int SP_KMAX = 125;  // offsets of the widest kernel served (5^3)
 constexpr int SP_BAD_RANGE = 1, SP_BAD_DUP = 2, SP_BAD_SPAN = 4;
@@ -40,7 +41,7 @@ __device__ __forceinline__ bool sp_coord_ok(int c, int ts) { return c < SP_COORD
 
 // bounding box of the (floored) coordinates + the range flag
 __global__ __launch_bounds__(SP_BLOCK) void sp_bounds_kernel(const int *__restrict__ coords, int64_t N, int ts, int down,
-                                                              int *__restrict__ meta)
+                                                              int cloud_limit, int *__restrict__ meta)
 {
     int v[8] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000, (int)0x80000000, 0};
     for (int64_t i = (int64_t)blockIdx.x * SP_BLOCK + threadIdx.x; i < N; i += (int64_t)gridDim.x * SP_BLOCK) {
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_bounds_kernel(const int *__restri
             v[3 + a] = max(v[3 + a], c);
         }
         int b = coords[i * 4 + 3];
-        if (b < 0 || b >= SP_BATCH_LIMIT) {
+        if (b < 0 || b >= cloud_limit) {
             v[7] |= SP_BAD_RANGE;
             b = 0;
         }
@@ -80,12 +81,14 @@ __device__ __forceinline__ bool sp_key(const int *__restrict__ meta, int x, int 
 }
 
 __global__ __launch_bounds__(SP_BLOCK) void sp_key_kernel(const int *__restrict__ coords, int64_t N, int ts, int down,
-                                                           int *__restrict__ meta, unsigned long long *__restrict__ keys,
+                                                           int cloud_limit, int *__restrict__ meta,
+                                                           unsigned long long *__restrict__ keys,
                                                            unsigned int *__restrict__ vals)
 {
     const int64_t i = (int64_t)blockIdx.x * SP_BLOCK + threadIdx.x;
     if (i == 0) {
-        // extents <= 2^19 each, batches <= 2^9: the product may pass 2^63 only for a box no real scene has -- flag it
+        // extents <= 2^19 each, batches <= cloud_limit <= 2^24: the product passes 2^63 for a box no real scene has (2^9
+        // clouds) or for many clouds over a wide box (4e18 / 2^24 clouds = a cube of 6 000 cells) -- flag it
         const double total = ((double)meta[3] - meta[0] + 1.0) * ((double)meta[4] - meta[1] + 1.0) *
                              ((double)meta[5] - meta[2] + 1.0) * ((double)meta[6] + 1.0);
         if (total >= 4.0e18) atomicOr(&meta[7], SP_BAD_SPAN);
@@ -99,7 +102,7 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_key_kernel(const int *__restrict_
         if (down > 0) c[a] = sp_floor_to(c[a], down);
     }
     int b = coords[i * 4 + 3];
-    if (b < 0 || b >= SP_BATCH_LIMIT) b = 0;
+    if (b < 0 || b >= cloud_limit) b = 0;
     unsigned long long key = 0;
     (void)sp_key(meta, c[0], c[1], c[2], b, &key);
     keys[i] = key;
@@ -519,8 +522,8 @@ __global__ __launch_bounds__(64 * SPW_WG_MAX_WAVES) void sp_wgrad_wide_kernel(co
     }
 }
 
-// the sort covers the bits the key can have: the host knows the hard limits only (3 * 19 + 9 bits would pass 64, the
-// span flag rejects such a box), so 63
+// the sort covers the bits the key can have: the host knows the hard limits only (3 * 19 + 9 bits, or + 24 with a cloud
+// bound of its own, would pass 64; the span flag rejects such a box), so 63
 constexpr unsigned SP_KEY_BITS = 63;
 
 }  // namespace tp3d
@@ -533,10 +536,11 @@ TP3D_EXPORT size_t tp3d_sparse_workspace_bytes(int64_t N)
     return carve_sort_workspace(nullptr, N, true, true).bytes;
 }
 
-TP3D_EXPORT int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int ts, int down, int64_t *keys_out,
-                                          int32_t *rows_out, int32_t *coords_out, int32_t *meta, void *workspace,
-                                          size_t workspace_bytes, void *stream)
+TP3D_EXPORT int tp3d_sparse_set_build_clouds_i32(const int32_t *coords, int64_t N, int ts, int down, int cloud_limit,
+                                                 int64_t *keys_out, int32_t *rows_out, int32_t *coords_out, int32_t *meta,
+                                                 void *workspace, size_t workspace_bytes, void *stream)
 {
+    if (cloud_limit < 1 || cloud_limit > SP_CLOUD_LIMIT_MAX) return TP3D_E_BADARG;
     if (N <= 0 || N >= 0x7fffffff || ts < 1 || ts >= SP_COORD_LIMIT || down < 0 || down >= SP_COORD_LIMIT || !coords || !keys_out || !rows_out || !meta ||
         !workspace || (down > 0 && !coords_out))
         return TP3D_E_BADARG;
@@ -546,9 +550,10 @@ TP3D_EXPORT int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int 
     const unsigned blocks = (unsigned)((N + SP_BLOCK - 1) / SP_BLOCK);
     hipLaunchKernelGGL(box_init_kernel, dim3(1), dim3(64), 0, s, meta, SP_META);
     if (int rc = check_launch()) return rc;
-    hipLaunchKernelGGL(sp_bounds_kernel, dim3(blocks > 1024 ? 1024 : blocks), dim3(SP_BLOCK), 0, s, coords, N, ts, down, meta);
+    hipLaunchKernelGGL(sp_bounds_kernel, dim3(blocks > 1024 ? 1024 : blocks), dim3(SP_BLOCK), 0, s, coords, N, ts, down,
+                       cloud_limit, meta);
     if (int rc = check_launch()) return rc;
-    hipLaunchKernelGGL(sp_key_kernel, dim3(blocks), dim3(SP_BLOCK), 0, s, coords, N, ts, down, meta, w.keys_in,
+    hipLaunchKernelGGL(sp_key_kernel, dim3(blocks), dim3(SP_BLOCK), 0, s, coords, N, ts, down, cloud_limit, meta, w.keys_in,
                        w.vals_in);
     if (int rc = check_launch()) return rc;
     unsigned long long *sorted = down > 0 ? w.keys_out : reinterpret_cast<unsigned long long *>(keys_out);
@@ -562,6 +567,16 @@ TP3D_EXPORT int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int 
                        reinterpret_cast<unsigned long long *>(keys_out), rows_out, coords_out, meta);
     return check_launch();
 }
+
+TP3D_EXPORT int tp3d_sparse_set_build_i32(const int32_t *coords, int64_t N, int ts, int down, int64_t *keys_out,
+                                          int32_t *rows_out, int32_t *coords_out, int32_t *meta, void *workspace,
+                                          size_t workspace_bytes, void *stream)
+{
+    return tp3d_sparse_set_build_clouds_i32(coords, N, ts, down, SP_BATCH_LIMIT, keys_out, rows_out, coords_out, meta, workspace,
+                                            workspace_bytes, stream);
+}
+
+TP3D_EXPORT int tp3d_sparse_cloud_limit_max(void) { return SP_CLOUD_LIMIT_MAX; }
 
 TP3D_EXPORT int tp3d_sparse_kmap_i32(const int32_t *qcoords, int64_t Nq, int ksize, int step, int sign, const int64_t *keys,
                                      const int32_t *rows, const int32_t *meta, int64_t Ns, int32_t *table, void *stream)

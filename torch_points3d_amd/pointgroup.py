@@ -8,10 +8,14 @@ loop and no dense (clusters, N) mask.
   instance_iou_csr     torch_points_kernels.instance_iou on the CSR
   offset_loss, instance_iou_loss   restatements of core/losses/panoptic_losses.py
   PanopticResults, PanopticLabels  the reference's structures; `clusters` may be a ClusterSet
-  PointGroup           backbone -> Semantic / Offset heads -> clusters -> ScorerMLP + segment_max (or the semantic certainty)
+  PointGroup           backbone -> Semantic / Offset heads -> clusters -> a scorer -> ScorerHead (or the semantic certainty)
+  pointgroup_config    the resolved numbers of the two entries of conf/models/panoptic/pointgroup.yaml
 
-Served: scorer_type "MLP" and None.  Not served: the sparse scorers ("encoder", "unet"), the MinkowskiEngine backbones and
-the panoptic tracker (see PointGroup below and INTEGRATION.md 1a).
+Served: every scorer_type -- "MLP" and None as they stand, "unet" and "encoder" (a sparse network over one cloud per cluster:
+torchpoints.cluster_voxelize builds the tensor, SparseTensor(clouds=K) holds more than 2^9 clouds) when the scorer's config
+is handed in (`scorer_unet=` / `scorer_encoder=`, e.g. from pointgroup_config); a call without one is refused as before.  The
+sparse scorers are assembled from this library's SparseConv3d family, as the backbone is.  Not served: the MinkowskiEngine
+backends and the panoptic tracker.
 """
 from typing import Any, NamedTuple
 
@@ -21,7 +25,7 @@ from torch import nn
 
 from . import torchpoints as tp
 from .partial_dense import MLP
-from .sparseconv import Seq, SparseConv3dUnet
+from .sparseconv import Seq, SparseConv3dEncoder, SparseConv3dUnet
 from .torchpoints import ClusterSet
 
 IGNORE_LABEL = -1  # datasets/segmentation/__init__.py:1
@@ -163,34 +167,103 @@ class PanopticLabels(NamedTuple):
     vote_label: torch.Tensor
 
 
+def _scorer_config(kind, in_feat, n_blocks):
+    """scorer_unet / scorer_encoder of pointgroup.yaml with `in_feat` and `N` filled in (both entries share the shape)"""
+    f = in_feat
+    cfg = dict(down_conv=dict(module_name="ResNetDown", dimension=3, down_conv_nn=[[f, 2 * f], [2 * f, 4 * f]], kernel_size=3,
+                              stride=2, N=n_blocks))
+    if kind == "unet":
+        cfg["up_conv"] = dict(module_name="ResNetUp", dimension=3, up_conv_nn=[[4 * f, 2 * f], [2 * f + 2 * f, f]], kernel_size=3,
+                              stride=2, N=n_blocks)
+    else:
+        cfg["innermost"] = dict(module_name="GlobalBaseModule", activation=dict(name="LeakyReLU", negative_slope=0.2), aggr="max",
+                                nn=[4 * f, f])
+    return cfg
+
+
+def pointgroup_config(name, feat):
+    """The resolved numbers of conf/models/panoptic/pointgroup.yaml: `PointGroup` (the default backbone, scorers at in_feat
+    96 with one block per stage) or `PointGroup-PAPER` (feat_size 16, two blocks per stage, a 7-level backbone with strides
+    [1, 2, 2, 2, 2, 2, 2]); `feat` = FEAT, the dataset's feature dimension.  The `backbone`, `scorer_unet` and
+    `scorer_encoder` values are the dicts sparseconv's networks take as `config`; `backbone` is None for the default
+    ("unet" without a config: SparseConv3dUnet("unet_4") here, the MinkowskiEngine U-Net in the reference)."""
+    common = dict(scorer_type="unet", prepare_epoch=120, min_iou_threshold=0.25, max_iou_threshold=0.75,
+                  loss_weights=dict(semantic=1, offset_norm_loss=1, offset_dir_loss=1, score_loss=1))
+    if name == "PointGroup":
+        return dict(common, backbone=None, scorer_unet=_scorer_config("unet", 96, 1), scorer_encoder=_scorer_config("encoder", 96, 1))
+    if name == "PointGroup-PAPER":
+        f = 16
+        backbone = dict(
+            down_conv=dict(module_name="ResNetDown", dimension=3, kernel_size=3, stride=[1, 2, 2, 2, 2, 2, 2], N=2,
+                           down_conv_nn=[[feat, f]] + [[i * f, (i + 1) * f] for i in range(1, 7)]),
+            up_conv=dict(module_name="ResNetUp", dimension=3, kernel_size=3, stride=[2, 2, 2, 2, 2, 2, 1], N=2,
+                         up_conv_nn=[[7 * f, 6 * f]] + [[2 * i * f, (i - 1) * f] for i in range(6, 1, -1)] + [[2 * f, f]]))
+        return dict(common, feat_size=f, backbone=backbone, scorer_unet=_scorer_config("unet", f, 2),
+                    scorer_encoder=_scorer_config("encoder", f, 2))
+    raise ValueError("unknown PointGroup configuration %r (\"PointGroup\" or \"PointGroup-PAPER\")" % (name,))
+
+
 class PointGroup(nn.Module):
     """PointGroup on the CSR.  `backbone`: any module mapping the batch (x, coords, batch, pos) to (N, C) features with an
-    `output_nc` attribute; default SparseConv3dUnet("unet_4", input_nc).  Semantic, Offset, ScorerMLP and ScorerHead carry
-    the reference's attribute names and layer order (pointgroup.py:45-56).
+    `output_nc` attribute; default SparseConv3dUnet("unet_4", input_nc).  Semantic, Offset, ScorerUnet, ScorerEncoder,
+    ScorerMLP and ScorerHead carry the reference's attribute names and layer order (pointgroup.py:41-56).
 
-    scorer_type "MLP": ScorerMLP on backbone_features[members], max per cluster (segment_max over `starts`), ScorerHead;
-    None: the mean semantic row per cluster, then its maximum (no gradient, as in the reference).
-    "encoder" and "unet" are not served: they run a sparse network on one "cloud" per cluster, and this library's sparse
-    coordinate keys hold 2^9 clouds while a scene has more clusters than that; the MinkowskiEngine backends they and the
-    reference's backbone are written for are out of scope."""
+    scorer_type (the default here stays "MLP"; the reference's is "encoder", its YAML says "unet"):
+      "unet"     cluster_voxelize -> ScorerUnet (a SparseConv3dUnet) -> max per cluster (segment_max over the voxel
+                 offsets) -> ScorerHead
+      "encoder"  cluster_voxelize -> ScorerEncoder (a SparseConv3dEncoder whose innermost max gives one row per cluster) ->
+                 ScorerHead
+      "MLP"      ScorerMLP on backbone_features[members], max per cluster (segment_max over `starts`), ScorerHead
+      None       the mean semantic row per cluster, then its maximum (no gradient, as in the reference)
+    scorer_unet / scorer_encoder: the config dict of that network (pointgroup_config(...)["scorer_unet"]).  The sparse
+    scorers are opt-in: scorer_type "unet" / "encoder" WITHOUT its config raises NotImplementedError, as every call did
+    before these arguments existed -- a sparse tensor holds 2^9 clouds unless it is built with clouds=K, and handing in the
+    scorer's config is what asks for that.  Only the scorer that scorer_type names is built
+    (the reference builds all three), so a model's state_dict holds no parameter its loss cannot reach except ScorerMLP's.
+    ScorerHead takes the scorer's output_nc.  cluster_voxel_size: the voxel edge of the clusters' tensor (0.05; None or 0:
+    the data's `coords` unchanged).
+
+    The sparse scorers score every cluster as one cloud of ONE sparse tensor with clouds = the number of clusters: no
+    per-cluster loop, no trip through the host (the reference moves the batch to the CPU and back), the score loss
+    reaches the backbone through the voxel mean's gradient.  Device-to-host reads of one scoring: two in cluster_voxelize
+    and one per coordinate set the scorer visits (three for the YAML's two strided stages)."""
 
     loss_names = ["loss", "offset_norm_loss", "offset_dir_loss", "semantic_loss", "score_loss"]
 
     def __init__(self, input_nc, num_classes, stuff_classes=(), backbone=None, scorer_type="MLP", scorer_nc=None,
                  cluster_radius_search=0.03, prepare_epoch=120, loss_weights=None, min_iou_threshold=0.25,
-                 max_iou_threshold=0.75):
+                 max_iou_threshold=0.75, scorer_unet=None, scorer_encoder=None, cluster_voxel_size=0.05):
         super().__init__()
-        if scorer_type in ("encoder", "unet"):
-            raise NotImplementedError(
-                "PointGroup scorer_type %r is not served: it scores every cluster as one cloud of a sparse network, the "
-                "sparse coordinate keys hold 2^9 clouds and a scene has more clusters than that; the MinkowskiEngine "
-                "backends are out of scope.  Use \"MLP\" or None." % (scorer_type,))
-        if scorer_type not in ("MLP", None):
+        if scorer_type not in ("unet", "encoder", "MLP", None):
             raise ValueError("unknown scorer_type %r" % (scorer_type,))
+        if scorer_type in ("unet", "encoder") and (scorer_unet if scorer_type == "unet" else scorer_encoder) is None:
+            raise NotImplementedError(
+                "PointGroup scorer_type %r is not served without its network: it scores every cluster as one cloud of a "
+                "sparse network, and by default the sparse coordinate keys hold 2^9 clouds while a scene has more clusters "
+                "than that.  Pass scorer_%s=<config> (pointgroup_config(name, feat)[\"scorer_%s\"], or any dict "
+                "SparseConv3d%s takes) to score on a tensor built with clouds = the number of clusters, or use \"MLP\" or "
+                "None.  The MinkowskiEngine backends are out of scope."
+                % (scorer_type, scorer_type, scorer_type, "Unet" if scorer_type == "unet" else "Encoder"))
         self.Backbone = backbone if backbone is not None else SparseConv3dUnet("unet_4", input_nc)
         nc = self.Backbone.output_nc
-        scorer_nc = nc if scorer_nc is None else scorer_nc
         self._scorer_type = scorer_type
+        self.cluster_voxel_size = cluster_voxel_size
+        self._scorer_cfg = None
+        if scorer_type in ("unet", "encoder"):
+            cfg = scorer_unet if scorer_type == "unet" else scorer_encoder
+            if cfg["down_conv"]["down_conv_nn"][0][0] != nc:
+                raise ValueError("the %s scorer takes %d channels, the backbone gives %d"
+                                 % (scorer_type, cfg["down_conv"]["down_conv_nn"][0][0], nc))
+            self._scorer_cfg = cfg
+            if scorer_type == "unet":
+                self.ScorerUnet = SparseConv3dUnet(cfg, nc)
+            else:
+                self.ScorerEncoder = SparseConv3dEncoder(cfg, nc)
+            sparse_nc = (self.ScorerUnet if scorer_type == "unet" else self.ScorerEncoder).output_nc
+            if scorer_nc is not None and scorer_nc != sparse_nc:
+                raise ValueError("scorer_nc %d is not the %s scorer's output width %d" % (scorer_nc, scorer_type, sparse_nc))
+            scorer_nc = sparse_nc
+        scorer_nc = nc if scorer_nc is None else scorer_nc
         self.ScorerMLP = MLP([nc, nc, scorer_nc])
         self.ScorerHead = Seq().append(nn.Linear(scorer_nc, 1)).append(nn.Sigmoid())
         self.Offset = Seq().append(MLP([nc, nc], bias=False))
@@ -222,6 +295,15 @@ class PointGroup(nn.Module):
         return self.output
 
     def _compute_score(self, clusters, backbone_features, semantic_logits):
+        if self._scorer_type in ("unet", "encoder"):
+            data = self.input
+            voxels, voxel_starts = tp.cluster_voxelize(clusters, backbone_features, data.pos, self.cluster_voxel_size,
+                                                       getattr(data, "coords", None))
+            if self._scorer_type == "unet":
+                cluster_feats = tp.segment_max(self.ScorerUnet(voxels), voxel_starts)
+            else:
+                cluster_feats = self.ScorerEncoder(voxels, clouds=len(clusters))
+            return self.ScorerHead(cluster_feats).squeeze(-1)
         if self._scorer_type:
             rows = self.ScorerMLP(backbone_features[clusters.members])
             cluster_feats = tp.segment_max(rows, clusters.starts)

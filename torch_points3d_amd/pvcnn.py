@@ -172,7 +172,7 @@ def point_to_voxel(x, z):
         if target is None:
             raise RuntimeError("point_to_voxel: no coordinate set of tensor stride %d" % x.s)
         _voxelize_tables(z, _quantize(z.C.float().contiguous(), x.s), target, x.s)
-    return SparseTensor(_voxelize(z, x.s), x.C, x.s, x.cmaps, x.kmaps)
+    return SparseTensor(_voxelize(z, x.s), x.C, x.s, x.cmaps, x.kmaps, x.clouds)
 
 
 def voxel_to_point(x, z, nearest=False):

@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import fused as _fused
+from . import torchpoints as _tp
 from .kpconv import _require_gpu
 from .kpconv_blocks import FastBatchNorm1d
 
@@ -34,14 +35,24 @@ from .kpconv_blocks import FastBatchNorm1d
 WIDE_ROUTE = "auto"
 
 COORD_LIMIT = 1 << 18  # |x|, |y|, |z| below this at tensor stride 1
-BATCH_LIMIT = 1 << 9   # batch index below this
+BATCH_LIMIT = 1 << 9   # batch index below this ...
+CLOUD_LIMIT_MAX = 1 << 24  # ... or below SparseTensor(clouds=K), K up to this (SP_CLOUD_LIMIT_MAX of csrc/sparseconv.hip)
 _BAD_RANGE, _BAD_DUP, _BAD_SPAN = 1, 2, 4
 
 
-def _raise_bad(flags):
+def _check_clouds(clouds):
+    """the opt-in bound on the batch index: None (2^9, the default) or an int in [1, 2^24]"""
+    if clouds is None:
+        return None
+    if isinstance(clouds, bool) or int(clouds) != clouds or not 1 <= int(clouds) <= CLOUD_LIMIT_MAX:
+        raise ValueError("clouds must be None or an integer in [1, 2^24], got %r" % (clouds,))
+    return int(clouds)
+
+
+def _raise_bad(flags, clouds=None):
     if flags & _BAD_RANGE:
-        raise ValueError("sparse coordinates out of range: need 0 <= batch < 2^9 and every voxel [c, c + tensor stride) to "
-                         "hold a coordinate with |x|, |y|, |z| < 2^18")
+        raise ValueError("sparse coordinates out of range: need 0 <= batch < %s and every voxel [c, c + tensor stride) to "
+                         "hold a coordinate with |x|, |y|, |z| < 2^18" % ("2^9" if clouds is None else "clouds = %d" % clouds))
     if flags & _BAD_SPAN:
         raise ValueError("sparse coordinates span too large a box: extent_x * extent_y * extent_z * batches must stay "
                          "below 2^62")
@@ -49,20 +60,21 @@ def _raise_bad(flags):
         raise ValueError("duplicate coordinates in a sparse tensor: every (x, y, z, batch) row must be distinct")
 
 
-def check_coords_host(coords, stride=1):
+def check_coords_host(coords, stride=1, clouds=None):
     """The accepted-input rule on a host tensor (what the device build flags in its read-back): a voxel of tensor stride
     `stride` covers [c, c + stride) per axis and must hold a coordinate of (-2^18, 2^18) -- |c| < 2^18 at stride 1, and
-    -2^18 itself (the floor of -(2^18 - 1)) at a coarser one."""
+    -2^18 itself (the floor of -(2^18 - 1)) at a coarser one.  The batch index stays below 2^9, or below `clouds`."""
+    limit = BATCH_LIMIT if _check_clouds(clouds) is None else int(clouds)
     c = coords.long()
     flags = 0
     if c.numel():
         xyz = c[:, :3]
         if (bool((xyz >= COORD_LIMIT).any()) or bool((xyz + stride - 1 <= -COORD_LIMIT).any()) or bool((c[:, 3] < 0).any())
-                or bool((c[:, 3] >= BATCH_LIMIT).any())):
+                or bool((c[:, 3] >= limit).any())):
             flags |= _BAD_RANGE
         elif torch.unique(c, dim=0).shape[0] != c.shape[0]:
             flags |= _BAD_DUP
-    _raise_bad(flags)
+    _raise_bad(flags, clouds)
 
 
 class _CoordSet(object):
@@ -74,8 +86,9 @@ class _CoordSet(object):
         self.coords, self.keys, self.rows, self.meta, self.n = coords, keys, rows, meta, n
 
 
-def _build_set(coords, ts, down):
-    """`coords` of tensor stride ts.  down == 0: their set; else the distinct floor(c / down) * down, ascending (batch, x, y, z)."""
+def _build_set(coords, ts, down, clouds=None):
+    """`coords` of tensor stride ts.  down == 0: their set; else the distinct floor(c / down) * down, ascending (batch, x, y, z).
+    clouds: the bound on the batch index when it is not 2^9 (tp3d_sparse_set_build_clouds_i32)."""
     dev = coords.device
     N = coords.shape[0]
     if N == 0:
@@ -87,10 +100,14 @@ def _build_set(coords, ts, down):
     nbytes = _lib.load().tp3d_sparse_workspace_bytes(N)
     ws = _lib.workspace("sparse_set", nbytes, dev)
     with _lib.on_device(dev):
-        _lib.call("tp3d_sparse_set_build_i32", _lib.ptr(coords), N, int(ts), int(down), _lib.ptr(keys), _lib.ptr(rows),
-                  _lib.ptr(out_coords), _lib.ptr(meta), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+        if clouds is None:
+            _lib.call("tp3d_sparse_set_build_i32", _lib.ptr(coords), N, int(ts), int(down), _lib.ptr(keys), _lib.ptr(rows),
+                      _lib.ptr(out_coords), _lib.ptr(meta), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+        else:
+            _lib.call("tp3d_sparse_set_build_clouds_i32", _lib.ptr(coords), N, int(ts), int(down), int(clouds), _lib.ptr(keys),
+                      _lib.ptr(rows), _lib.ptr(out_coords), _lib.ptr(meta), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
     host = meta.cpu()  # the one read of a new set: row count and bad-input flags
-    _raise_bad(int(host[7]))
+    _raise_bad(int(host[7]), clouds)
     n = int(host[8])
     if down:
         return _CoordSet(out_coords[:n], keys[:n], rows[:n], meta, n)
@@ -133,27 +150,36 @@ def _build_kmap(in_set, out_set, ksize, ts, same_set):
 class SparseTensor(object):
     """F (N, C) fp32 features, C (N, 4) int32 [x, y, z, batch], s the tensor stride; `cmaps` / `kmaps` are shared by every
     tensor derived from this one.  Host tensors are validated on construction; device tensors in the read-back of the
-    first coordinate-set build."""
+    first coordinate-set build.  `clouds` = None: batch indices below 2^9.  clouds = K (up to 2^24): batch indices in
+    [0, K) -- one cloud per cluster of PointGroup's scorers; every coordinate set of the tensor is then built with that
+    bound and every tensor derived from it (`_like`, strided outputs, `cat`) inherits it.  The key holds extent_x *
+    extent_y * extent_z * clouds < 4e18, so many clouds want a scene-sized box.  (`clouds` is the last parameter, behind
+    the caches, so that positional callers keep working; pass it by keyword.)"""
 
-    def __init__(self, feats, coords, stride=1, cmaps=None, kmaps=None):
+    def __init__(self, feats, coords, stride=1, cmaps=None, kmaps=None, clouds=None):
         if coords.dim() != 2 or coords.shape[1] != 4 or feats.dim() != 2 or feats.shape[0] != coords.shape[0]:
             raise ValueError("SparseTensor needs feats (N, C) and coords (N, 4) = [x, y, z, batch]")
         self.F = feats
         self.C = coords if coords.dtype == torch.int32 else coords.int()
         self.s = int(stride)
+        self.clouds = _check_clouds(clouds)
         self.cmaps = {} if cmaps is None else cmaps
         self.kmaps = {} if kmaps is None else kmaps
         if cmaps is None and self.C.device.type != "cuda":
-            check_coords_host(self.C, self.s)
+            check_coords_host(self.C, self.s, self.clouds)
 
     def to(self, device):
         device = torch.device(device)
         if device == self.F.device:
             return self
-        return SparseTensor(self.F.to(device), self.C.to(device), self.s)
+        return SparseTensor(self.F.to(device), self.C.to(device), self.s, clouds=self.clouds)
 
     def _like(self, feats):
-        return SparseTensor(feats, self.C, self.s, self.cmaps, self.kmaps)
+        return SparseTensor(feats, self.C, self.s, self.cmaps, self.kmaps, self.clouds)
+
+    def _on(self, feats, ts):
+        """`feats` on this tensor's cached coordinate set of tensor stride ts"""
+        return SparseTensor(feats, self.cmaps[ts].coords, ts, self.cmaps, self.kmaps, self.clouds)
 
     def __add__(self, other):
         return self._like(self.F + other.F)
@@ -163,7 +189,7 @@ class SparseTensor(object):
         cs = self.cmaps.get(ts)
         if cs is None and ts == self.s:
             _require_gpu(self.C)
-            cs = self.cmaps[ts] = _build_set(self.C.contiguous(), ts, 0)
+            cs = self.cmaps[ts] = _build_set(self.C.contiguous(), ts, 0, self.clouds)
         return cs
 
     def _kmap(self, ksize, ts, stride):
@@ -182,7 +208,7 @@ class SparseTensor(object):
                 if out_set is None:
                     if ts != self.s:
                         raise RuntimeError("no coordinate set of tensor stride %d" % (ts * stride))
-                    out_set = self.cmaps[ts * stride] = _build_set(in_set.coords, ts, ts * stride)
+                    out_set = self.cmaps[ts * stride] = _build_set(in_set.coords, ts, ts * stride, self.clouds)
             km = self.kmaps[key] = _build_kmap(in_set, out_set, ksize, ts, stride == 1)
         return km
 
@@ -328,8 +354,7 @@ class Conv3d(nn.Module):
             km = inputs._kmap(k, ts, st)
             y = _GatherConv.apply(inputs.F, self.kernel.reshape(k ** 3, self.in_channels, self.out_channels), km.forward,
                                   km.inverse)
-            out = inputs._like(y) if st == 1 else SparseTensor(y, inputs.cmaps[ts * st].coords, ts * st, inputs.cmaps,
-                                                               inputs.kmaps)
+            out = inputs._like(y) if st == 1 else inputs._on(y, ts * st)
         else:
             if st > 1 and ts % st != 0:
                 raise RuntimeError("transposed sparse convolution of stride %d on a tensor of stride %d" % (st, ts))
@@ -340,7 +365,7 @@ class Conv3d(nn.Module):
             km = inputs._kmap(k, fine, st)
             y = _GatherConv.apply(inputs.F, self.kernel.reshape(k ** 3, self.in_channels, self.out_channels), km.inverse,
                                   km.forward)
-            out = SparseTensor(y, inputs.cmaps[fine].coords, fine, inputs.cmaps, inputs.kmaps)
+            out = inputs._on(y, fine)
         if self.bias is not None:
             out.F = out.F + self.bias
         return out
@@ -540,8 +565,11 @@ class _BaseSparseConv3d(nn.Module):
         down = dict(down, N=down.get("N", [1] * n_down))
         if up is not None:
             up = dict(up, N=up.get("N", [1] * len(up["up_conv_nn"])))
+        def per_layer(opts, key, n):  # a scalar (PointGroup's scorers: `kernel_size: 3`) holds for every layer
+            return not isinstance(opts[key], (list, tuple)) or len(opts[key]) == n
+
         for key in ("N", "kernel_size", "stride"):
-            if len(down[key]) != n_down or (up is not None and len(up[key]) != len(up["up_conv_nn"])):
+            if not per_layer(down, key, n_down) or (up is not None and not per_layer(up, key, len(up["up_conv_nn"]))):
                 raise ValueError("sparseconv3d configuration %r: `%s` has not one entry per layer (the reference cannot build "
                                  "this file either)" % (config, key))
         self.down_modules = nn.ModuleList(ResNetDown(**_stage_options(down, i)) for i in range(n_down))
@@ -552,7 +580,11 @@ class _BaseSparseConv3d(nn.Module):
         inner = cfg.get("innermost")
         self.inner_modules = nn.ModuleList()
         if inner is not None:
-            self.inner_modules.append(_GlobalMean(inner["nn"], inner["negative_slope"]))
+            aggr = inner.get("aggr", "mean")
+            if aggr not in _GLOBAL_AGGR:
+                raise NotImplementedError("sparseconv3d innermost: aggr %r is not served (\"mean\" or \"max\")" % (aggr,))
+            slope = inner["negative_slope"] if "negative_slope" in inner else inner["activation"]["negative_slope"]
+            self.inner_modules.append(_GLOBAL_AGGR[aggr](inner["nn"], slope))
             default_output_nc = inner["nn"][-1]
         self.weight_initialization()
         self._output_nc = default_output_nc
@@ -602,6 +634,24 @@ class _GlobalMean(nn.Module):
         return out / count.clamp(min=1).unsqueeze(-1)
 
 
+class _GlobalMax(_GlobalMean):
+    """GlobalBaseModule(aggr="max"): the same `nn` on every row, then the maximum per cloud (torchpoints.segment_max).  The
+    rows of a strided coordinate set ascend in (batch, x, y, z), so a cloud's rows are consecutive and their offsets come
+    from a search in the batch column on the device: no device read.  ordered=False (the rows of an input set, in the
+    caller's order): they are first sorted by cloud, stably, on the device.  A cloud without rows gives zeros."""
+
+    def forward(self, x, batch, clouds, ordered=True):
+        x = self.nn(x)
+        if not ordered:
+            batch, perm = torch.sort(batch, stable=True)
+            x = x[perm]
+        seg = torch.searchsorted(batch.contiguous(), torch.arange(clouds + 1, dtype=batch.dtype, device=batch.device))
+        return _tp.segment_max(x, seg)
+
+
+_GLOBAL_AGGR = {"mean": _GlobalMean, "max": _GlobalMax}
+
+
 class SparseConv3dUnet(_BaseSparseConv3d):
     """forward: SparseTensor (or an object with x, coords, batch) -> (N, output_nc) features in the input's row order"""
 
@@ -622,17 +672,22 @@ class SparseConv3dUnet(_BaseSparseConv3d):
 
 
 class SparseConv3dEncoder(_BaseSparseConv3d):
-    """forward: -> (clouds, output_nc), one row per cloud.  `clouds` (default: largest batch index + 1, one device read)."""
+    """forward: -> (clouds, output_nc), one row per cloud.  `clouds` (default: largest batch index + 1, one device read;
+    given, the forward reads nothing back beyond the one read of every new coordinate set).  A tensor built with
+    SparseTensor(clouds=K) brings its K along."""
 
     def __init__(self, config="encoder_4", input_nc=3, in_feat=32, block="ResBlock", output_nc=None):
         super().__init__(config, input_nc, in_feat, block, output_nc)
 
     def forward(self, data, clouds=None):
         data = self._input(data)
+        s_in = data.s
         for down in self.down_modules:
             data = down(data)
         batch = data.C[:, 3].long()
         if clouds is None:
-            clouds = int(batch.max()) + 1
-        x = self.inner_modules[0](data.F, batch, clouds)
+            clouds = data.clouds if data.clouds is not None else int(batch.max()) + 1
+        inner = self.inner_modules[0]
+        # (a strided set's rows ascend by cloud; the input set keeps the caller's row order)
+        x = inner(data.F, batch, clouds, ordered=data.s != s_in) if isinstance(inner, _GlobalMax) else inner(data.F, batch, clouds)
         return self.mlp(x) if self.has_mlp_head else x

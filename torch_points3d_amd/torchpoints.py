@@ -703,6 +703,83 @@ class ClusterSet(object):
                    routes.pop() if len(routes) == 1 else "mixed")
 
 
+class _ClusterVoxelMean(torch.autograd.Function):
+    """out[v] = mean of x[members[e]] over the slots e of voxel v (csrc/cluster_voxel.hip): x is read through voxel -> slot
+    -> point, the gradient is summed per point through the inverted point -> slots index; no (E, C) rows either way."""
+
+    @staticmethod
+    def forward(ctx, x, members, order, vstart, slot_voxel):
+        xf, ldx = _rows_ld(x)
+        dev = xf.device
+        (N, C), E, V = xf.shape, members.numel(), vstart.numel() - 1
+        out = torch.empty((V, C), dtype=torch.float32, device=dev)
+        with _lib.on_device(dev):
+            _lib.call("tp3d_cluster_voxel_mean_fwd_f32", _lib.ptr(xf), ldx, _lib.ptr(members), _lib.ptr(order), _lib.ptr(vstart),
+                      N, E, V, C, _lib.ptr(out), _lib.stream_ptr(dev))
+        ctx.save_for_backward(members, slot_voxel, vstart)
+        ctx.shape = (N, C)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        members, slot_voxel, vstart = ctx.saved_tensors
+        N, C = ctx.shape
+        dout = _f32(dout)
+        dev = dout.device
+        E, V = members.numel(), vstart.numel() - 1
+        dx = torch.empty((N, C), dtype=torch.float32, device=dev)
+        pstart, porder = _invert_rows(members, N)  # the slots of every point, ascending (stable radix sort)
+        with _lib.on_device(dev):
+            _lib.call("tp3d_cluster_voxel_mean_bwd_f32", _lib.ptr(dout), _lib.ptr(slot_voxel), _lib.ptr(vstart), _lib.ptr(pstart),
+                      _lib.ptr(porder), N, E, V, C, _lib.ptr(dx), _lib.stream_ptr(dev))
+        return dx, None, None, None, None
+
+
+def cluster_voxelize(clusters, x, pos, size, coords=None):
+    """The batch PointGroup scores (pointgroup.py:123-141): every cluster of the ClusterSet `clusters` becomes one cloud of
+    a sparse tensor, voxelised by GridSampling3D(size, quantize_coords=True, mode="mean") -- without the per-cluster loop,
+    the concatenated rows or the host.  x (N, C) fp32 (rows may be strided), pos (N, 3) -> (SparseTensor with clouds =
+    len(clusters), voxel_starts (K + 1,) int64: the voxels of cluster c are rows voxel_starts[c] : voxel_starts[c + 1]).
+
+    Slot e of cluster c with point p = members[e] lies in voxel (c, round(pos[p] / size)) (fp32 division, half to even).
+    One row per distinct voxel; rows ascend by cluster and inside a cluster by (z, y, x), the order of the reference's
+    voxel key.  The feature row is the mean of x[p] over the voxel's slots, summed in ascending slot order (a voxel of more
+    than 64 slots in the 16 pieces of tp3d_pv_runsum_f32), divided by the count; C[:, :3] is the rounded coordinate,
+    C[:, 3] = c.  A point of two clusters appears in both clouds.  Differentiable wrt x: the gradient of a point is the
+    sum over its slots, ascending, of its voxels' gradient rows / count -- no float atomics, exact zeros for a point in no
+    cluster, repeats bit-equal.
+
+    size None or 0 (the reference's cluster_voxel_size falsy): no voxelisation; the rows are the member slots, C[:, :3] =
+    coords[members] (`coords` is needed), the features gather_rows(x, members), voxel_starts = clusters.starts.
+
+    Device-to-host reads: two, those of voxel_cluster (the extent of the voxel key, the voxel count); none without a
+    size.  The coordinate sets of the tensor add one each when a convolution first asks for them."""
+    from .grid_sampling import voxel_cluster
+    from .sparseconv import SparseTensor  # (sparseconv imports this module)
+    dev = _dev(x, pos, clusters.members, coords)
+    if x.dim() != 2 or x.shape[1] < 1 or pos.dim() != 2 or pos.shape[1] != 3 or pos.shape[0] != x.shape[0]:
+        raise ValueError("x must be (N, C) with C >= 1 and pos (N, 3)")
+    K = len(clusters)
+    members = _i64(clusters.members)
+    if K == 0 or members.numel() == 0:
+        raise ValueError("cluster_voxelize needs at least one cluster with a member")
+    owner = _i64(clusters.member_cluster)
+    if not size:
+        if coords is None:
+            raise ValueError("without a voxel size the quantised `coords` of the points are needed")
+        C4 = torch.cat([coords[members].int(), owner.int().unsqueeze(-1)], 1)
+        return SparseTensor(gather_rows(x, members), C4, clouds=K), _i64(clusters.starts)
+    slot_pos = pos.detach().float()[members]
+    slot_voxel, last, order, vstart = voxel_cluster(slot_pos, owner, size)
+    # tensor / tensor is a true fp32 division on the device (GridSampling3D._process)
+    size_t = torch.full((), float(size), dtype=torch.float32, device=dev)
+    voxel_owner = owner[last]
+    C4 = torch.cat([torch.round(slot_pos[last] / size_t).int(), voxel_owner.int().unsqueeze(-1)], 1)
+    voxel_starts = torch.searchsorted(voxel_owner, torch.arange(K + 1, dtype=torch.int64, device=dev))
+    feats = _ClusterVoxelMean.apply(x, members, order, vstart, slot_voxel)
+    return SparseTensor(feats, C4, clouds=K), voxel_starts
+
+
 REGION_GROW_FLAGS = {1: "a label outside [0, 4094]", 2: "a cloud id outside [0, 1023]", 4: "a coordinate beyond 2^24 cells",
                      8: "more than 16382 cells along an axis"}
 
