@@ -776,6 +776,41 @@ size_t tp3d_segment_sum_workspace_bytes(int64_t N, int64_t B, int C);
 int tp3d_segment_sum_f32(const float *rows, const int64_t *seg, const float *scale, int64_t N, int64_t B, int col0, int C, int ld,
                          float *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Detection: box post-processing of VoteNet (csrc/detection.hip)
+ *                       [utils/box_utils.py:28-182, modules/VoteNet/votenet_results.py:231-255, metrics/box_detection/ap.py:81-107]
+ *   tp3d_box_nms_f32: nms_samecls for B scenes of P boxes in one launch, one workgroup per scene.  boxes (B, P, 6) fp32
+ *     [xmin ymin zmin xmax ymax zmax], classes (B, P), order (B, P): the visiting order of each scene (box indices in
+ *     [0, P), best first; the host wrapper sorts).  A live box i clears every later box j of the order with
+ *     classes[i] == classes[j] and o > overlap_threshold, where in fp32, one rounding per operation, no fused multiply-add:
+ *     area = ((x2 - x1) * (y2 - y1)) * (z2 - z1), l, w, h = max(0, min(hi) - max(lo)) per axis, inter = (l * w) * h,
+ *     o = inter / ((area_i + area_j) - inter), o = o * (1 or 0 for equal classes).  0 / 0 compares false.
+ *     keep (B, P) bytes, 1 = kept.  P <= TP3D_BOX_NMS_MAX_BOXES (else TP3D_E_TOOBIG); nothing of size P * P is written.
+ *   tp3d_box3d_iou_f64: corners1 (n, 8, 3), corners2 (m, 8, 3) fp32 -> iou (n, m) float64, box3d_iou of every pair: rows
+ *     0-3 the bottom face counter-clockwise seen from +z, rows 4-7 the top face.  The footprint of box 1 is clipped by
+ *     the footprint of box 2 with polygon_clip's Sutherland-Hodgman (edge order, strict inside test, computeIntersection)
+ *     in float64 on the promoted corners; the area is 0.5 * |sum_k (x_k * y_k+1 - x_k+1 * y_k)| in vertex order, 0 for an
+ *     empty clip; height max(0, min(c1[4].z, c2[4].z) - max(c1[0].z, c2[0].z)); volumes as box3d_vol (three edge lengths);
+ *     iou = inter / ((vol1 + vol2) - inter).  Where rounding splits two collinear edges (a rotated box against itself) the
+ *     clip divides by zero and the result is NaN; the reference's hull raises on the same pairs.
+ *   tp3d_box_best_gt_f64: for detection d (corners (D, 8, 3), class, scene) the first maximum of that IoU over the
+ *     ground-truth boxes gt_scene_start[scene] .. gt_scene_start[scene + 1]) of its class (gt sorted by scene; S scenes):
+ *     ovmax (D) float64, -inf without a candidate; jmax (D) the row of that box in gt_corners, -1 without a candidate.
+ *     No (D, G) matrix is written.
+ *   tp3d_ap_match: order (D) lists the detections grouped by (scene, class), inside a group by descending score (the
+ *     host wrapper sorts).  Each group is walked in that order; tp[d, t] = 1 when ovmax[d] > thresholds[t] (strict) and
+ *     jmax[d] has not been taken by an earlier detection of the group at that threshold.  thresholds (T) float64 DEVICE
+ *     memory; taken (T * G) bytes of scratch (cleared here); tp (D, T) bytes. */
+#define TP3D_BOX_NMS_MAX_BOXES 4096
+int tp3d_box_nms_max_boxes(void);
+int tp3d_box_nms_f32(const float *boxes, const int64_t *classes, const int64_t *order, int B, int P, float overlap_threshold,
+                     uint8_t *keep, void *stream);
+int tp3d_box3d_iou_f64(const float *corners1, const float *corners2, int64_t n, int64_t m, double *iou, void *stream);
+int tp3d_box_best_gt_f64(const float *det_corners, const int64_t *det_class, const int64_t *det_scene, int64_t D,
+                         const float *gt_corners, const int64_t *gt_class, const int64_t *gt_scene_start, int64_t G, int64_t S,
+                         double *ovmax, int64_t *jmax, void *stream);
+int tp3d_ap_match(const int64_t *order, const int64_t *det_class, const int64_t *det_scene, int64_t D, const double *ovmax,
+                  const int64_t *jmax, int64_t G, const double *thresholds, int T, uint8_t *taken, uint8_t *tp, void *stream);
+
 /* =====================================================================================================
  * Launch plans (host arithmetic only, no device work): what an entry point WILL do for given sizes -- how it
  * splits the rows, how many partial rows it writes, how it carves its workspace.  tests/test_plans_cpu.py sweeps

@@ -107,6 +107,10 @@ SIGNATURES = {
     "tp3d_segment_transform_wgrad_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
     "tp3d_segment_bcast_cat_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _i, _i, _p, _p],
     "tp3d_segment_sum_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
+    "tp3d_box_nms_f32": [_p, _p, _p, _i, _i, _f, _p, _p],
+    "tp3d_box3d_iou_f64": [_p, _p, _l, _l, _p, _p],
+    "tp3d_box_best_gt_f64": [_p, _p, _p, _l, _p, _p, _p, _l, _l, _p, _p, _p],
+    "tp3d_ap_match": [_p, _p, _p, _l, _p, _p, _l, _p, _i, _p, _p, _p],
     # launch plans (host arithmetic; the last argument is a HOST int64 array)
     "tp3d_gemm_tn_plan": [_l, _i, _i, _p],
     "tp3d_gemm_tn_x3_plan": [_l, _i, _i, _p],
@@ -155,6 +159,7 @@ MISC = {
     "tp3d_segment_sum_chunk": (_i, []),
     "tp3d_segment_transform_wgrad_workspace_bytes": (_z, [_l, _l, _i]),
     "tp3d_segment_sum_workspace_bytes": (_z, [_l, _l, _i]),
+    "tp3d_box_nms_max_boxes": (_i, []),
 }
 ABI_VERSION = 39
 

@@ -44,3 +44,29 @@ class DirichletLoss(torch.nn.Module):
 
     def forward(self, pos, f, batch_idx=None):
         return dirichlet_loss(self._r, pos, f, batch_idx=batch_idx, aggr=self._aggr)
+
+
+def huber_loss(error, delta=1.0):
+    """Element-wise Huber penalty of core/losses/huber_loss.py:34-51: x^2 / 2 up to |x| = delta, linear with slope delta
+    beyond."""
+    mag = error.abs()
+    q = mag.clamp(max=delta)
+    return 0.5 * (q * q) + delta * (mag - q)
+
+
+def nn_distance(pc1, pc2, l1smooth=False, delta=1.0, l1=False):
+    """Nearest row of the other set, both ways (core/losses/huber_loss.py:4-31): pc1 (B, N, C), pc2 (B, M, C) ->
+    (dist1 (B, N), idx1 (B, N), dist2 (B, M), idx2 (B, M)) under the squared (default), l1 or Huber distance summed over
+    C.  The (B, N, M, C) differences come from broadcasting, so the reference's two `repeat`ed copies are never written;
+    the arithmetic per element is the same."""
+    diff = pc1[:, :, None, :] - pc2[:, None, :, :]
+    if l1smooth:
+        cost = huber_loss(diff, delta)
+    elif l1:
+        cost = diff.abs()
+    else:
+        cost = diff * diff
+    cost = cost.sum(-1)
+    dist1, idx1 = cost.min(dim=2)
+    dist2, idx2 = cost.min(dim=1)
+    return dist1, idx1, dist2, idx2

@@ -1218,3 +1218,103 @@ def segment_mean_rows(rows, seg):
     if rows.dim() != 2 or rows.shape[1] < 1 or seg.dim() != 1 or seg.numel() < 1:
         raise ValueError("rows must be (N, C) and seg (B + 1,)")
     return _SegmentMeanRows.apply(rows, _i64(seg))
+
+
+# ------------------------------------------------------------------------------------------- detection (csrc/detection.hip)
+BOX_NMS_MAX_BOXES = 4096  # TP3D_BOX_NMS_MAX_BOXES
+
+
+def box_nms(boxes, scores, classes, overlap_threshold=0.25):
+    """nms_samecls (utils/box_utils.py:28-85) for every scene in one launch.  boxes (B, P, 6) fp32
+    [xmin ymin zmin xmax ymax zmax], scores (B, P), classes (B, P) -> keep (B, P) bool.  Boxes are visited by descending
+    score, among equal scores the HIGHER index first (a stable ascending sort read from the back, as the reference's
+    argsort is); a live box clears every later box of its class whose overlap inter / (area_i + area_j - inter) exceeds
+    the threshold, in the reference's fp32 arithmetic with the threshold rounded to fp32, so the decisions are those of
+    the reference bit for bit.  Two boxes without volume give 0 / 0, which compares false.  P <= 4096.  Nothing is read
+    back to the host.  Device tensors only."""
+    if boxes.dim() != 3 or boxes.shape[2] != 6:
+        raise ValueError("boxes must be (B, P, 6), got %s" % (tuple(boxes.shape),))
+    B, P, _ = boxes.shape
+    if tuple(scores.shape) != (B, P) or tuple(classes.shape) != (B, P):
+        raise ValueError("scores and classes must be (B, P)")
+    if P > BOX_NMS_MAX_BOXES:
+        raise ValueError("box_nms serves at most %d boxes per scene, got %d" % (BOX_NMS_MAX_BOXES, P))
+    dev = _dev(boxes, scores, classes)
+    boxes, classes = _f32(boxes), _i64(classes)
+    keep = torch.zeros((B, P), dtype=torch.uint8, device=dev)
+    if B == 0 or P == 0:
+        return keep.bool()
+    order = torch.sort(_f32(scores), dim=1, stable=True).indices.flip(1).contiguous()
+    with _lib.on_device(dev):
+        _lib.call("tp3d_box_nms_f32", _lib.ptr(boxes), _lib.ptr(classes), _lib.ptr(order), B, P, float(overlap_threshold),
+                  _lib.ptr(keep), _lib.stream_ptr(dev))
+    return keep.bool()
+
+
+def _corners(t, name):
+    if t.dim() != 3 or tuple(t.shape[1:]) != (8, 3):
+        raise ValueError("%s must be (n, 8, 3), got %s" % (name, tuple(t.shape)))
+    return _f32(t)
+
+
+def box3d_iou(corners1, corners2):
+    """box3d_iou (utils/box_utils.py:88-109) for every pair: corners1 (n, 8, 3), corners2 (m, 8, 3) fp32 -> (n, m) float64.
+    Corner rows as box_corners_from_param gives them (0-3 the bottom face counter-clockwise seen from +z, 4-7 the top
+    face).  The footprint of box 1 is clipped by the footprint of box 2 with the reference's Sutherland-Hodgman in
+    float64; the area is the shoelace sum of the clipped polygon.  A rotated box against itself (collinear edges that
+    rounding splits) gives NaN, where the reference's hull raises.  Device tensors only."""
+    dev = _dev(corners1, corners2)
+    c1, c2 = _corners(corners1, "corners1"), _corners(corners2, "corners2")
+    n, m = c1.shape[0], c2.shape[0]
+    out = torch.empty((n, m), dtype=torch.float64, device=dev)
+    if n and m:
+        with _lib.on_device(dev):
+            _lib.call("tp3d_box3d_iou_f64", _lib.ptr(c1), _lib.ptr(c2), n, m, _lib.ptr(out), _lib.stream_ptr(dev))
+    return out
+
+
+def box_best_gt(det_corners, det_class, det_scene, gt_corners, gt_class, gt_scene_start):
+    """For every detection the first maximum of the IoU over the ground-truth boxes of its scene and class
+    (eval_det_cls, metrics/box_detection/ap.py:85-97): (ovmax (D,) float64, jmax (D,) int64).  gt boxes are sorted by
+    scene, gt_scene_start (S + 1,) their offsets; jmax is a row of gt_corners, -1 (and ovmax -inf) without a candidate.
+    The IoU is computed on the fly: nothing of size D x G is written.  Device tensors only."""
+    dev = _dev(det_corners, det_class, det_scene, gt_corners, gt_class, gt_scene_start)
+    det, gt = _corners(det_corners, "det_corners"), _corners(gt_corners, "gt_corners")
+    D, G = det.shape[0], gt.shape[0]
+    det_class, det_scene, gt_class, start = _i64(det_class), _i64(det_scene), _i64(gt_class), _i64(gt_scene_start)
+    if tuple(det_class.shape) != (D,) or tuple(det_scene.shape) != (D,) or tuple(gt_class.shape) != (G,) or start.dim() != 1 \
+            or start.shape[0] < 1:
+        raise ValueError("class and scene vectors must match the boxes; gt_scene_start must be (S + 1,)")
+    ovmax = torch.empty((D,), dtype=torch.float64, device=dev)
+    jmax = torch.empty((D,), dtype=torch.int64, device=dev)
+    if D:
+        with _lib.on_device(dev):
+            _lib.call("tp3d_box_best_gt_f64", _lib.ptr(det), _lib.ptr(det_class), _lib.ptr(det_scene), D, _lib.ptr(gt),
+                      _lib.ptr(gt_class), _lib.ptr(start), G, start.shape[0] - 1, _lib.ptr(ovmax), _lib.ptr(jmax),
+                      _lib.stream_ptr(dev))
+    return ovmax, jmax
+
+
+def ap_match(det_corners, det_score, det_class, det_scene, gt_corners, gt_class, gt_scene_start, thresholds=(0.25, 0.5)):
+    """The true-positive flags of eval_det_cls (metrics/box_detection/ap.py:81-107) for every (scene, class) group at
+    once: (tp (D, T) bool, ovmax (D,) float64, jmax (D,) int64) in the order of the input.  Inside a group detections are
+    visited by descending score, equal scores in input order; a detection is a true positive at threshold t when
+    ovmax > t (strict) and its box jmax has not been taken by an earlier detection of the group.  Device tensors only."""
+    ovmax, jmax = box_best_gt(det_corners, det_class, det_scene, gt_corners, gt_class, gt_scene_start)
+    dev = ovmax.device
+    D, G = ovmax.shape[0], gt_corners.shape[0]
+    thr = torch.as_tensor([float(t) for t in thresholds], dtype=torch.float64).to(dev, non_blocking=True)
+    T = thr.shape[0]
+    tp = torch.zeros((D, T), dtype=torch.uint8, device=dev)
+    if D and T:
+        det_class, det_scene = _i64(det_class), _i64(det_scene)
+        if tuple(det_score.shape) != (D,):
+            raise ValueError("det_score must be (D,)")
+        order = torch.sort(det_score.detach(), descending=True, stable=True).indices
+        order = order[torch.sort(det_class[order], stable=True).indices]
+        order = order[torch.sort(det_scene[order], stable=True).indices].contiguous()
+        taken = torch.empty((max(T * G, 1),), dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            _lib.call("tp3d_ap_match", _lib.ptr(order), _lib.ptr(det_class), _lib.ptr(det_scene), D, _lib.ptr(ovmax),
+                      _lib.ptr(jmax), G, _lib.ptr(thr), T, _lib.ptr(taken), _lib.ptr(tp), _lib.stream_ptr(dev))
+    return tp.bool(), ovmax, jmax
