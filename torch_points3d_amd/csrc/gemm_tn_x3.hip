@@ -26,6 +26,7 @@
 namespace tp3d {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -132,27 +133,36 @@ __global__ __launch_bounds__(X3_BLOCK) void gemm_tn_x3_kernel(const float *__res
 #pragma unroll
             for (int i = 0; i < SS; ++i) os[i] = (unsigned)((((lt + i * 256) / 8) * K + k0 + TK + ((lt + i * 256) % 8) * 4) * 4);
         }
-        auto fetch = [&](int t, float4 *ry, float4 *ra, float4 *rs, float4 *rd) __attribute__((always_inline)) {
-            const int64_t r0 = ((int64_t)(pro.reverse ? steps - 1 - t : t) * S + blockIdx.y) * BR;  // (last row blocks first)
+        auto row0 = [&](int t) __attribute__((always_inline)) -> int64_t {
+            return ((int64_t)(pro.reverse ? steps - 1 - t : t) * S + blockIdx.y) * BR;  // (last row blocks first)
+        };
+        // a row block that lies inside both matrices as a whole: every load is unconditional (but the strip's columns past K and
+        // the dA rows of another tile row's step) and lands in the stage's own registers
+        auto fetch_full = [&](int t, bool red, float4 *ry, float4 *ra, float4 *rs, float4 *rd) __attribute__((always_inline)) {
+            const int64_t r0 = row0(t);
             const char *by_ = reinterpret_cast<const char *>(dY) + r0 * N * 4;
             const char *ba_ = reinterpret_cast<const char *>(A) + r0 * K * 4;
-            if (r0 + BR <= M && cols_full) {  // (wave-uniform) the whole block lies inside both matrices
 #pragma unroll
-                for (int i = 0; i < SY; ++i) ry[i] = *reinterpret_cast<const float4 *>(by_ + oy[i]);
+            for (int i = 0; i < SY; ++i) ry[i] = *reinterpret_cast<const float4 *>(by_ + oy[i]);
 #pragma unroll
-                for (int i = 0; i < SA; ++i) ra[i] = *reinterpret_cast<const float4 *>(ba_ + oa[i]);
-                if (mine(t)) {
-                    const char *bd_ = reinterpret_cast<const char *>(pro.dA) + r0 * K * 4;
+            for (int i = 0; i < SA; ++i) ra[i] = *reinterpret_cast<const float4 *>(ba_ + oa[i]);
+            if (red) {
+                const char *bd_ = reinterpret_cast<const char *>(pro.dA) + r0 * K * 4;
 #pragma unroll
-                    for (int i = 0; i < SA; ++i) rd[i] = *reinterpret_cast<const float4 *>(bd_ + oa[i]);
+                for (int i = 0; i < SA; ++i) rd[i] = *reinterpret_cast<const float4 *>(bd_ + oa[i]);
+            }
+            if (STRIP) {
+#pragma unroll
+                for (int i = 0; i < SS; ++i) {
+                    rs[i] = zero;
+                    if (k0 + TK + ((lt + i * 256) % 8) * 4 < K) rs[i] = *reinterpret_cast<const float4 *>(ba_ + os[i]);
                 }
-                if (STRIP) {
-#pragma unroll
-                    for (int i = 0; i < SS; ++i) {
-                        rs[i] = zero;
-                        if (k0 + TK + ((lt + i * 256) % 8) * 4 < K) rs[i] = *reinterpret_cast<const float4 *>(ba_ + os[i]);
-                    }
-                }
+            }
+        };
+        auto fetch = [&](int t, float4 *ry, float4 *ra, float4 *rs, float4 *rd) __attribute__((always_inline)) {
+            const int64_t r0 = row0(t);
+            if (r0 + BR <= M && cols_full) {  // (wave-uniform)
+                fetch_full(t, mine(t), ry, ra, rs, rd);
                 return;
             }
 #pragma unroll
@@ -205,16 +215,28 @@ __global__ __launch_bounds__(X3_BLOCK) void gemm_tn_x3_kernel(const float *__res
             return make_float4(z0 > 0.0f ? z0 : z0 * pro.slope, z1 > 0.0f ? z1 : z1 * pro.slope, z2 > 0.0f ? z2 : z2 * pro.slope,
                                z3 > 0.0f ? z3 : z3 * pro.slope);
         };
-        auto store = [&](int t, const float4 *ry, const float4 *ra, const float4 *rs, const float4 *rd) __attribute__((always_inline)) {
+        // A stage's registers are first read HERE, through an empty asm statement: without it the compiler moves the first
+        // arithmetic on a loaded value (the component shuffles of its packed fp32 operations) up to the load, i.e. in front
+        // of the barrier and of the loop's back edge, and waits there for loads it has only just issued.
+        auto pin = [&](float4 v) __attribute__((always_inline)) -> float4 {
+            f32x4 q = __builtin_bit_cast(f32x4, v);  // (one 128-bit operand: the load's own register tuple, tied in place)
+            asm volatile("" : "+v"(q));
+            return __builtin_bit_cast(float4, q);
+        };
+        auto store = [&](int t, bool red, const float4 *ry, const float4 *ra_, const float4 *rs, const float4 *rd) __attribute__((always_inline)) {
             unsigned short *by = smem + (t & 1) * BUF, *ba = by + 3 * PLANE_N;
-            if (mine(t)) {
+            float4 ra[SA];
+#pragma unroll
+            for (int i = 0; i < SA; ++i) ra[i] = pin(ra_[i]);
+            if (red) {
                 // dZ = dA * act'(z), sums of dZ and dZ * yhat: the expressions of colreduce_partial_kernel<., 1> (rows.hip)
                 const int col = ((lt % (TK / 4))) * 4;  // (256 % (TK / 4) == 0: every slot of this thread has these columns)
                 const float4 mu = *reinterpret_cast<const float4 *>(&sK[0][col]), sc = *reinterpret_cast<const float4 *>(&sK[1][col]);
                 const float4 be = *reinterpret_cast<const float4 *>(&sK[2][col]), is = *reinterpret_cast<const float4 *>(&sK[3][col]);
 #pragma unroll
                 for (int i = 0; i < SA; ++i) {
-                    const float y[4] = {ra[i].x, ra[i].y, ra[i].z, ra[i].w}, d[4] = {rd[i].x, rd[i].y, rd[i].z, rd[i].w};
+                    const float4 rdi = pin(rd[i]);
+                    const float y[4] = {ra[i].x, ra[i].y, ra[i].z, ra[i].w}, d[4] = {rdi.x, rdi.y, rdi.z, rdi.w};
                     const float m4[4] = {mu.x, mu.y, mu.z, mu.w}, s4[4] = {sc.x, sc.y, sc.z, sc.w};
                     const float b4[4] = {be.x, be.y, be.z, be.w}, i4[4] = {is.x, is.y, is.z, is.w};
 #pragma unroll
@@ -229,7 +251,7 @@ __global__ __launch_bounds__(X3_BLOCK) void gemm_tn_x3_kernel(const float *__res
 #pragma unroll
             for (int i = 0; i < SY; ++i) {
                 const int e = lt + i * 256;
-                put(by, PLANE_N, PN, e / (TN / 4), (e % (TN / 4)) * 4, ry[i]);
+                put(by, PLANE_N, PN, e / (TN / 4), (e % (TN / 4)) * 4, pin(ry[i]));
             }
 #pragma unroll
             for (int i = 0; i < SA; ++i) {
@@ -242,7 +264,8 @@ __global__ __launch_bounds__(X3_BLOCK) void gemm_tn_x3_kernel(const float *__res
                 for (int i = 0; i < SS; ++i) {
                     const int e = lt + i * 256;
                     const int col = TK + (e % 8) * 4;
-                    put(ba, PLANE_K, PK, e / 8, col, prologue ? act4(rs[i], col) : rs[i]);
+                    const float4 rsi = pin(rs[i]);
+                    put(ba, PLANE_K, PK, e / 8, col, prologue ? act4(rsi, col) : rsi);
                 }
             }
         };
@@ -253,11 +276,34 @@ __global__ __launch_bounds__(X3_BLOCK) void gemm_tn_x3_kernel(const float *__res
         if (steps > 1) fetch(1, ry1, ra1, rs1, rd1);
         if (steps > 2) fetch(2, ry2, ra2, rs2, rd2);
         auto iter = [&](int t, float4 *ry, float4 *ra, float4 *rs, float4 *rd) __attribute__((always_inline)) {
-            store(t, ry, ra, rs, rd);
+            store(t, mine(t), ry, ra, rs, rd);
             if (t + 3 < steps) fetch(t + 3, ry, ra, rs, rd);
             __syncthreads();
         };
-        for (int t = 0; t < steps; t += 3) {
+        // Main loop: three steps per pass, one per register stage, nothing conditional but the dA stream -- no value is
+        // carried through a join, so every load is issued into the registers its stage keeps and the wait in front of a
+        // store counts the loads of the two younger stages as still in flight.  It fetches the steps 3 .. steps - 2 only,
+        // whose row blocks are whole (the one ragged block of a launch is some workgroup's step 0 or steps - 1); the last
+        // four to six steps (every step of a workgroup with at most six), and every step of a tile that overhangs N or K,
+        // take the general loop below.
+        auto iter_full = [&](int t, float4 *ry, float4 *ra, float4 *rs, float4 *rd) __attribute__((always_inline)) {
+            store(t, mine(t), ry, ra, rs, rd);
+            fetch_full(t + 3, mine(t + 3), ry, ra, rs, rd);
+            __syncthreads();
+        };
+        int t = 0;
+        if (cols_full && steps > 6) {
+            // (all three stages have arrived before the first pass: the wait counts inside the loop are then those of its own
+            //  loads -- entered with the general fetches of above in flight, whose number the compiler cannot count, every pass
+            //  would start with a full wait.)  s_waitcnt vmcnt(0), the other counters left at their maxima
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+            for (; t + 6 < steps; t += 3) {
+                iter_full(t, ry0, ra0, rs0, rd0);
+                iter_full(t + 1, ry1, ra1, rs1, rd1);
+                iter_full(t + 2, ry2, ra2, rs2, rd2);
+            }
+        }
+        for (; t < steps; t += 3) {
             iter(t, ry0, ra0, rs0, rd0);
             if (t + 1 < steps) iter(t + 1, ry1, ra1, rs1, rd1);
             if (t + 2 < steps) iter(t + 2, ry2, ra2, rs2, rd2);
