@@ -67,7 +67,8 @@ __global__ __launch_bounds__(SP_BLOCK, 4) void gemm_rows_sp_kernel(const float *
     __shared__ __attribute__((aligned(16))) float sA[2][SP_TILE];
     __shared__ __attribute__((aligned(16))) float sB[2][BN * SP_LD];
     constexpr int TJ = BN / 64;  // 32-column MFMA tiles per compute wave (the wave grid stays 2 x 2)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // in a scalar register: the role and the wave's tile offsets
     const int ksteps = (K + SP_BK - 1) / SP_BK;
     const int tail_groups = (K - (ksteps - 1) * SP_BK + 7) / 8;
     if ((int64_t)blockIdx.x >= items) return;
@@ -212,19 +213,23 @@ __global__ __launch_bounds__(SP_BLOCK, 4) void gemm_rows_sp_kernel(const float *
             SP_FETCH_B();   // B of step 1
             SP_FETCH_A(0);  // A of step 2
             __syncthreads();  // B0: buffer 0 holds step 0
+            // Pairs of K-steps, then the odd last one: 1 + total barriers on every path, as in the compute waves.  A loop
+            // with an exit between its two halves is compiled with the stage registers rotated across the back edge, and
+            // its odd half then waits for every outstanding load; with a single exit both halves keep the newer A stage
+            // in flight.
 #pragma unroll 1
-            for (int64_t s = 0; s < total; s += 2) {
+            for (int64_t s = 0; s + 1 < total; s += 2) {
                 // during compute step s: step s+1 (A stage 1, B registers) into buffer 1; then B of s+2, A of s+3
                 SP_STASH2(1, 1);
                 SP_FETCH_B();
                 SP_FETCH_A(1);
                 __syncthreads();
-                if (s + 1 >= total) break;
                 SP_STASH2(0, 0);
                 SP_FETCH_B();
                 SP_FETCH_A(0);
                 __syncthreads();
             }
+            if (total & 1) __syncthreads();  // (the compute waves' last step; the step past it needs no staging)
 #undef SP_FETCH_A
 #undef SP_FETCH_B
 #undef SP_STASH2
@@ -286,6 +291,8 @@ __global__ __launch_bounds__(SP_BLOCK, 4) void gemm_rows_sp_kernel(const float *
         SP_STASH(0, 0);
         SP_FETCH(0);  // step 2
         __syncthreads();  // B0: buffer 0 holds step 0
+        // (this loop keeps its exit between the two halves: the compiled odd half then waits for the stage fetched one
+        // half-step earlier, but the pair-plus-tail form of the backward loop above measured no gain here -- DESIGN section 5)
 #pragma unroll 1
         for (int64_t s = 0; s < total; s += 2) {
             // during compute step s: write step s+1 (stage 1) into buffer 1, refill stage 1 with step s+3
@@ -350,22 +357,53 @@ __global__ __launch_bounds__(SP_BLOCK, 4) void gemm_rows_sp_kernel(const float *
         }
         if (++ks == ksteps) {
             ks = 0;
-            // ---- epilogue: D[row][col], col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+            // ---- epilogue: D[row][col], col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).  The tile's base and its
+            // row count are wave-uniform, a lane adds a 32-bit offset inside the tile (64-bit row numbers per lane cost the
+            // statistics form the registers of its running sums)
+            int ld = (int)ldc;
+            asm volatile("" : "+s"(ld));  // formed anew for every tile: hoisted out of the K walk, the row offsets stay in registers through it
+            const int rows_left = (int)min((int64_t)SP_BM, M - m0);  // <= 0: a padding block
+            float *tile = C + m0 * ldc + (int64_t)(wr * 64) * ld + (n0 + wc * TJ * 32);  // the wave's 64 x (32 TJ) corner
+            const unsigned lane_off = (unsigned)(4 * lh * ld + l31);
+            if (rows_left == SP_BM && n0 + BN <= N) {  // interior tile: every row and column is there
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < TJ; ++j) {
-                    const int n = n0 + (wc * TJ + j) * 32 + l31;
+                    for (int j = 0; j < TJ; ++j)
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        const int64_t m = m0 + (wr * 2 + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                        if (m < M && n < N) C[m * ldc + n] = acc[i][j][e];
-                        if (PRO >= 2 && j == 0 && wc == 0 && n0 == 0 && m < M) {  // the columns nobody computes stay defined
-                            if (l31 < pro.pad_lo) C[m * ldc - pro.pad_lo + l31] = 0.0f;
-                            if (l31 < pro.pad_hi) C[m * ldc + N + l31] = 0.0f;
-                        }
+                        for (int e = 0; e < 16; ++e) (tile + (i * 32 + (e & 3) + 8 * (e >> 2)) * ld + j * 32)[lane_off] = acc[i][j][e];
+                if (PRO >= 2 && wc == 0 && n0 == 0) {  // the columns nobody computes stay defined
+                    if (l31 < pro.pad_lo) {
+#pragma unroll
+                        for (int r = 0; r < 64; r += 8)
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) (tile + (r + q) * ld - pro.pad_lo)[lane_off] = 0.0f;
+                    }
+                    if (l31 < pro.pad_hi) {
+#pragma unroll
+                        for (int r = 0; r < 64; r += 8)
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) (tile + (r + q) * ld + N)[lane_off] = 0.0f;
                     }
                 }
+            } else {  // the ragged row block, an overhanging column tile, a padding block
+                const int rows_wave = rows_left - wr * 64 - 4 * lh;  // rows of the wave's corner at and below this lane's first
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < TJ; ++j) {
+                        const bool n_in = n0 + (wc * TJ + j) * 32 + l31 < N;
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) {
+                            const int r = i * 32 + (e & 3) + 8 * (e >> 2);
+                            if (r < rows_wave && n_in) (tile + r * ld + j * 32)[lane_off] = acc[i][j][e];
+                            if (PRO >= 2 && j == 0 && wc == 0 && n0 == 0 && r < rows_wave) {  // the columns nobody computes stay defined
+                                if (l31 < pro.pad_lo) (tile + r * ld - pro.pad_lo)[lane_off] = 0.0f;
+                                if (l31 < pro.pad_hi) (tile + r * ld + N)[lane_off] = 0.0f;
+                            }
+                        }
+                    }
+            }
             if (STATS != 0) {
                 const int valid = (int)min((int64_t)64, max((int64_t)0, M - (m0 + wr * 64)));  // wave-uniform
                 const float pad = (float)(64 - valid);

@@ -54,7 +54,8 @@ __global__ __launch_bounds__(B3_BLOCK, 4) void gemm_rows_x3_kernel(const float *
         __syncthreads();
     }
     // plane p of operand o (0 = A, 1 = B) in buffer u: smem + ((u * 2 + o) * 3 + p) * B3_PLANE
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // in a scalar register: the role and the wave's tile offsets
     const int ksteps = (K + B3_BK - 1) / B3_BK;
     if ((int64_t)blockIdx.x >= items) return;
     const int64_t my_items = (items - blockIdx.x + gridDim.x - 1) / gridDim.x;
@@ -147,16 +148,19 @@ __global__ __launch_bounds__(B3_BLOCK, 4) void gemm_rows_x3_kernel(const float *
         B3_STASH(0, 0);
         B3_FETCH(0);
         __syncthreads();
+        // Pairs of K-steps, then the odd last one: 1 + total barriers on every path, as in the MFMA waves.  A loop with an
+        // exit between its two halves is compiled with the stage registers rotated across the back edge, and its odd half
+        // then waits for the stage fetched one half-step earlier; with a single exit both halves keep the newer stage in flight.
 #pragma unroll 1
-        for (int64_t s = 0; s < total; s += 2) {
+        for (int64_t s = 0; s + 1 < total; s += 2) {
             B3_STASH(1, 1);
             B3_FETCH(1);
             __syncthreads();
-            if (s + 1 >= total) break;
             B3_STASH(0, 0);
             B3_FETCH(0);
             __syncthreads();
         }
+        if (total & 1) __syncthreads();  // (the MFMA waves' last step; the step past it needs no staging)
 #undef B3_FETCH
 #undef B3_PUT
 #undef B3_STASH
@@ -213,17 +217,34 @@ __global__ __launch_bounds__(B3_BLOCK, 4) void gemm_rows_x3_kernel(const float *
         }
         if (++ks == ksteps) {
             ks = 0;
+            // ---- epilogue: a wave-uniform pointer per tile row plus one 32-bit lane offset (64-bit row numbers per lane cost
+            // the statistics form the registers of its running sums)
+            int ld = N;
+            asm volatile("" : "+s"(ld));  // formed anew for every tile: hoisted out of the K walk, the row offsets stay in registers through it
+            const int rows_left = (int)min((int64_t)B3_BM, M - m0);  // <= 0: a padding block
+            float *tile = C + m0 * N + (int64_t)(wr * 64) * ld + (n0 + wc * 64);  // the wave's 64 x 64 corner
+            const unsigned lane_off = (unsigned)(4 * lh * ld + l31);
+            if (rows_left == B3_BM && n0 + B3_BN <= N) {  // interior tile: every row and column is there
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int n = n0 + (wc * 2 + j) * 32 + l31;
+                    for (int j = 0; j < 2; ++j)
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        const int64_t m = m0 + (wr * 2 + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                        if (m < M && n < N) C[m * N + n] = acc[i][j][e];
+                        for (int e = 0; e < 16; ++e) (tile + (i * 32 + (e & 3) + 8 * (e >> 2)) * ld + j * 32)[lane_off] = acc[i][j][e];
+            } else {  // the ragged row block, an overhanging column tile, a padding block
+                const int rows_wave = rows_left - wr * 64 - 4 * lh;  // rows of the wave's corner at and below this lane's first
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const bool n_in = n0 + (wc * 2 + j) * 32 + l31 < N;
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) {
+                            const int r = i * 32 + (e & 3) + 8 * (e >> 2);
+                            if (r < rows_wave && n_in) (tile + r * ld + j * 32)[lane_off] = acc[i][j][e];
+                        }
                     }
-                }
+            }
             if (STATS != 0) {
                 const int valid = (int)min((int64_t)64, max((int64_t)0, M - (m0 + wr * 64)));  // wave-uniform
                 const float pad = (float)(64 - valid);
