@@ -471,6 +471,21 @@ int tp3d_attn_pool_fwd_f32(const float *g, const float *f, const int64_t *nbr, i
 int tp3d_attn_pool_bwd_f32(const float *g, const float *f, const float *dout, const int64_t *nbr, int64_t Nq, int k, int C,
                            int ldg, int ldf, float *dg, float *df, void *stream);
 
+/* The whole eval-mode edge chain of RandlaKernel.message + aggr="add" in one kernel (csrc/randla_lfa.hip): nothing of
+ * size Nq*k is written to memory.  k must be 16; nbr (Nq, 16) rows of the support, no -1 slots.
+ *   rel  = [q_pos[q], s_pos[j], q_pos[q] - s_pos[j], |q_pos[q] - s_pos[j]|]                       (10)
+ *   rij  = L2(L1(rel))                              L1: 10 -> P1, L2: P1 -> P2          (point_pos_nn)
+ *   f    = [x[j] | rij]                             C = Cx + P2; x NULL: x[j] = s_pos[j], Cx must be 3
+ *   g    = L4(L3(f))                                L3: C -> A1, L4: A1 -> C            (attention_nn)
+ *   out[q, :] = sum over n = 0..15, in that order, of softmax_c(g) * f                 (Nq, C)
+ * L(v) = LeakyReLU_0.2(scale * (W v) + shift): nn.Linear's weight W (N, K) with the bias and the eval-mode BatchNorm
+ * folded by the caller, scale = gamma / sqrt(var + eps), shift = beta + scale * (bias - mean).
+ * consts: one dense float buffer, per layer L1..L4 in turn  W (N*K), scale (N), shift (N).
+ * Limits: C, P1, P2 <= 64, A1 <= 128 (TP3D_E_TOOBIG beyond).  fp32 products on the matrix pipe, no atomics. */
+int tp3d_randla_lfa_eval_f32(const float *q_pos, const float *s_pos, const float *x, const int64_t *nbr, int64_t Nq,
+                             int64_t M, int k, int Cx, int P1, int P2, int A1, const float *consts, float *out,
+                             void *stream);
+
 /* Skinny row GEMM of the edge-wise MLPs (modules/RandLANet/modules.py:20-22; nn.Linear inside MLP,
  * core/common_modules/base_modules.py:29-43):  Y (M, N) = A (M, K; row stride lda >= K) * W (N, K)^T,  N, K <= 32.
  * One row per lane, k ascending per output.  Y is dense (row stride N).

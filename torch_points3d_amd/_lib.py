@@ -72,6 +72,7 @@ SIGNATURES = {
     "tp3d_randla_relpos_f32": [_p, _p, _p, _l, _i, _l, _p, _p],
     "tp3d_attn_pool_fwd_f32": [_p, _p, _p, _l, _i, _i, _i, _i, _p, _p],
     "tp3d_attn_pool_bwd_f32": [_p, _p, _p, _p, _l, _i, _i, _i, _i, _p, _p, _p],
+    "tp3d_randla_lfa_eval_f32": [_p, _p, _p, _p, _l, _l, _i, _i, _i, _i, _i, _p, _p, _p],
     "tp3d_relation_rows_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p],
     "tp3d_fps_ragged_f32": [_p, _p, _p, _l, _i, _i, _p, _p, _p],
     "tp3d_table_edge_start_i64": [_p, _l, _i, _p, _p],
