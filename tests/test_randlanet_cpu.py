@@ -215,3 +215,88 @@ def test_fixture_replayed_on_cpu_tensors(case, oracle, monkeypatch):
         ev = net(ru.bag(gold, "cpu"))
     scale = float(gold["eval/out"].abs().max())
     assert float((ev - gold["eval/out"]).abs().max()) <= 1e-5 * scale
+
+
+# ---------------------------------------------------------------- the folded constants of the one-kernel pass
+
+def _edge_mlps(seed=3):
+    """a RandlaKernel in eval mode with the BatchNorm buffers and affine parameters of its edge MLPs off their defaults"""
+    from torch_points3d_amd.randla import RandlaKernel
+    torch.manual_seed(seed)
+    ker = RandlaKernel(point_pos_nn=[10, 8, 6], attention_nn=[12, 8, 12], global_nn=[12, 16]).eval()
+    g = torch.Generator().manual_seed(seed + 1)
+    with torch.no_grad():
+        for bn in _edge_bns(ker):
+            bn.running_mean.copy_(torch.randn(bn.num_features, generator=g) * 0.3)
+            bn.running_var.copy_(torch.rand(bn.num_features, generator=g) + 0.5)
+            bn.weight.copy_(torch.rand(bn.num_features, generator=g) + 0.5)
+            bn.bias.copy_(torch.randn(bn.num_features, generator=g) * 0.2)
+    return ker
+
+
+def _edge_bns(ker):
+    return [layer[1].batch_norm for mlp in (ker.point_pos_nn, ker.attention_nn) for layer in mlp]
+
+
+def _fresh_fold(ker):
+    from torch_points3d_amd import randla
+    with torch.no_grad():
+        return torch.cat([t.detach().float() for mlp in (ker.point_pos_nn, ker.attention_nn) for layer in mlp
+                          for t in randla._fold_layer(layer)])
+
+
+def _refolded(ker, old, values_moved=True):
+    """_lfa_consts hands out a new buffer that is the fold of the module's current tensors, and keeps that one"""
+    from torch_points3d_amd import randla
+    new = randla._lfa_consts(ker.point_pos_nn, ker.attention_nn)
+    assert new is not old
+    assert torch.equal(new, _fresh_fold(ker))
+    assert torch.equal(new, old) != values_moved
+    assert randla._lfa_consts(ker.point_pos_nn, ker.attention_nn) is new
+    return new
+
+
+def test_lfa_consts_follow_parameter_writes_loads_and_moves():
+    from torch_points3d_amd import randla
+    ker = _edge_mlps()
+    old = randla._lfa_consts(ker.point_pos_nn, ker.attention_nn)
+    assert torch.equal(old, _fresh_fold(ker))
+    assert randla._lfa_consts(ker.point_pos_nn, ker.attention_nn) is old
+    # an in-place write under no_grad, to a parameter of each kind
+    for pick in (lambda k: k.point_pos_nn[0][0].weight, lambda k: k.point_pos_nn[1][0].bias,
+                 lambda k: k.attention_nn[0][1].batch_norm.weight, lambda k: k.attention_nn[1][1].batch_norm.bias):
+        with torch.no_grad():
+            pick(ker).mul_(1.25).add_(0.125)
+        old = _refolded(ker, old)
+    # load_state_dict of another module's state
+    ker.load_state_dict(_edge_mlps(seed=9).state_dict())
+    old = _refolded(ker, old)
+    # .double().float(): the values round-trip exactly, the storages are new ones (the old ones are held here, so that
+    # no new storage can land on an old address)
+    held = [t.data for t in list(ker.parameters()) + list(ker.buffers())]
+    ker.double().float()
+    assert all(a.data_ptr() != b.data_ptr() for a, b in zip(held, list(ker.parameters()) + list(ker.buffers()))
+               if a.is_floating_point())
+    _refolded(ker, old, values_moved=False)
+
+
+@pytest.mark.parametrize("trigger", ["replay", "train_pass"])
+@pytest.mark.parametrize("stat", ["running_mean", "running_var"])
+@pytest.mark.parametrize("layer", range(4))
+def test_lfa_consts_follow_statistics_written_behind_the_version_counters(layer, stat, trigger):
+    """What the BatchNorm kernels and a replayed captured step do to the running statistics: the values change, no
+    version counter moves.  The constants are refolded once the module's training-pass count or the replay count says
+    so (fused.eval_state_key)."""
+    from torch_points3d_amd import fused, randla
+    ker = _edge_mlps()
+    old = randla._lfa_consts(ker.point_pos_nn, ker.attention_nn)
+    bn = _edge_bns(ker)[layer]
+    buf = getattr(bn, stat)
+    version = buf._version
+    buf.data.mul_(1.5).add_(0.25)
+    assert buf._version == version  # the write was invisible to the counter, as a raw-pointer write is
+    if trigger == "replay":
+        fused.note_graph_replay()
+    else:
+        bn._tp3d_train_passes = getattr(bn, "_tp3d_train_passes", 0) + 1
+    _refolded(ker, old)

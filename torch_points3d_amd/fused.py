@@ -243,6 +243,14 @@ def note_graph_replay():
     _replay_epoch += 1
 
 
+def eval_state_key(tensors, bns):
+    """What anything folded from eval-mode parameters and running statistics is cached under: address and version
+    counter of every tensor, and -- because the BatchNorm kernels and a replayed captured step write the statistics
+    without moving a version counter -- the training passes of every BatchNorm in `bns` and the replay count."""
+    return (tuple((t.data_ptr(), t._version) for t in tensors)
+            + tuple(getattr(bn, "_tp3d_train_passes", 0) for bn in bns) + (_replay_epoch,))
+
+
 ROWS_GEMM_MIN_COLS = 32   # narrower outputs (class scores, edge MLPs) stay on the library / skinny kernels
 ROWS_GEMM_WITHOUT_STATS = True  # the rows kernel also where it has no BatchNorm statistics to fold in.  False: library GEMM
                                 # there -- the choice for inference replayed from a HIP graph (KPConv unet_4 forward 1.46 ->
@@ -264,8 +272,7 @@ def _bn_stats(Y, M, C, gamma, beta, bn, training, dev, st, bias=None):
     module's parameters and running statistics, so they are computed once and reused until any of those changes."""
     key = None
     if not training:
-        key = tuple((t.data_ptr(), t._version) for t in (gamma, beta, bn.running_mean, bn.running_var)
-                    + ((bias,) if bias is not None else ())) + (getattr(bn, "_tp3d_train_passes", 0), _replay_epoch)
+        key = eval_state_key((gamma, beta, bn.running_mean, bn.running_var) + ((bias,) if bias is not None else ()), (bn,))
         hit = getattr(bn, "_tp3d_eval_stats", None)
         if hit is not None and hit[0] == key:
             return hit[1]

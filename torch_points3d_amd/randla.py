@@ -145,16 +145,18 @@ def _lfa_servable(mlp):
     return True
 
 
-_LFA_CONSTS = weakref.WeakKeyDictionary()  # point_pos_nn module -> (key of its tensors' versions, folded constants)
+_LFA_CONSTS = weakref.WeakKeyDictionary()  # point_pos_nn module -> (fused.eval_state_key of both MLPs, folded constants)
 
 
 def _lfa_consts(point_pos_nn, attention_nn):
     """the folded constants of the two MLPs as one dense buffer, per layer W, s, t (include/tp3d_hip.h); kept until a
-    parameter or buffer is written (its version counter moves) or moved (its address changes)"""
+    parameter or buffer is written (its version counter moves), moved (its address changes), or may have been written
+    behind the version counters: a training pass of one of the four BatchNorms (the HIP BatchNorm kernels update the
+    running statistics through raw pointers) or a replayed captured step (fused.eval_state_key)"""
     tensors = [t for mlp in (point_pos_nn, attention_nn) for layer in mlp
                for t in (layer[0].weight, layer[0].bias, layer[1].batch_norm.weight, layer[1].batch_norm.bias,
                          layer[1].batch_norm.running_mean, layer[1].batch_norm.running_var) if t is not None]
-    key = tuple((t.data_ptr(), t._version) for t in tensors)
+    key = _fused.eval_state_key(tensors, [layer[1].batch_norm for mlp in (point_pos_nn, attention_nn) for layer in mlp])
     hit = _LFA_CONSTS.get(point_pos_nn)
     if hit is not None and hit[0] == key:
         return hit[1]
