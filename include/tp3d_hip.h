@@ -841,6 +841,14 @@ int tp3d_gemm_tn_x3_plan(int64_t M, int N, int K, int64_t *plan);
 /* plan[9]: column tiles, row blocks, work items, workgroups, statistics chunks written, 1 = one chunk set per
  * workgroup, wave rows per tile, K-ranges of a split launch (K = 0: not asked), tile columns */
 int tp3d_gemm_rows_plan(int64_t M, int N, int K, int64_t *plan);
+/* Few-row launches (at most 256 work items of 128 x 128, no K-split) run as 64 x 64 tiles, four workgroups per item;
+ * plan[4]: 64 x 64 work items, workgroups (<= 1024), 1 = taken with statistics, 1 = taken without (a K-split launch
+ * never is).  C, the statistics chunks and tp3d_gemm_rows_stat_chunks / _stat_floats are the same either way. */
+int tp3d_gemm_rows_small_plan(int64_t M, int N, int K, int64_t *plan);
+/* on = 1 (default): the few-row tile rules of tp3d_gemm_rows_f32 / _epi_f32 (above) and tp3d_gemm_tn_f32 (a smaller
+ * tile where tiles x splits < 256; splits and rows per split untouched); on = 0: the plans without them.  Results are
+ * bit-identical.  Process-wide and not synchronised: set it before plans are queried or a step is captured. */
+int tp3d_set_few_row_tiles(int on);
 /* plan[3]: rows per chunk, chunks, workspace floats written by tp3d_bn_stats_f32 (pooled_ns = 0) or
  * tp3d_bn_act_bwd_f32 (pooled_ns = its ns; 1 for the dense form) */
 int tp3d_bn_plan(int64_t M, int C, int pooled_ns, int64_t *plan);

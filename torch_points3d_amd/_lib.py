@@ -116,6 +116,8 @@ SIGNATURES = {
     "tp3d_gemm_tn_plan": [_l, _i, _i, _p],
     "tp3d_gemm_tn_x3_plan": [_l, _i, _i, _p],
     "tp3d_gemm_rows_plan": [_l, _i, _i, _p],
+    "tp3d_gemm_rows_small_plan": [_l, _i, _i, _p],
+    "tp3d_set_few_row_tiles": [_i],
     "tp3d_bn_plan": [_l, _i, _i, _p],
     "tp3d_scatter_plan": [_i, _i, _i, _i, _p],
 }

@@ -21,6 +21,7 @@
 // summation whose round-off is ~3x smaller than one sequential chain over K.
 #include <algorithm>
 
+#include "gemm_plans.h"
 #include "tp3d_common.h"
 
 namespace tp3d {
@@ -28,7 +29,6 @@ namespace tp3d {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int GR_BLOCK_T = 256;
-constexpr int GR_BM = 128, GR_BK = 32;
 constexpr int GR_LD = GR_BK + 4;  // 36-float pitch
 
 // Output EPILOGUE of the eval-mode layers (mean == nullptr: none): C = LeakyReLU((acc - mean[n]) * scale[n] + beta[n]) --
@@ -443,6 +443,173 @@ __global__ __launch_bounds__(GR_BLOCK_T, 2) void gemm_rows_wide_kernel(const flo
     }
 }
 
+// The 64 x 64 form of the plain wide kernel, for launches of few rows (4096 / 16384: the global set-abstraction level and
+// the coarse decoder levels).  Their 128 x 128 plans have 64-256 work items, i.e. 256-1024 waves for 1024 SIMDs, and a
+// wave holds one SIMD however well it runs: here every 128 x 128 item becomes four workgroups (rows_small_plan), whose
+// four waves (2 x 2) own ONE 32 x 32 MFMA tile each.  Per element of C nothing changes -- the 32-deep K-step, the
+// 36-float pitch, the operand read at g * 8 + lh * 4, the tail-group rule, the x, y, z, w order: the same fmaf chain,
+// the same bits.  One work item per workgroup (at most 1024 of them), so there is no item walk; what hides the memory
+// latency is two K-steps of global loads in flight (two register stages, two LDS buffers, one barrier per K-step: a
+// K-step is 16 MFMAs per wave, about a memory latency).  Every fetch issues its four loads unconditionally on clamped
+// addresses and the zeros go in when the stage is written to LDS, so the counted waits in front of the LDS writes stay
+// exact; the fetches past the last K-step land on the last columns and are never staged.
+// STATS: 0 none, 1 the chunk of gemm_rows_wide_kernel<1> -- one per (128-row block, 64-row half), summed in that kernel's
+// order: the 64 rows of a column belong to the two wave rows here, so the upper wave takes the shift from its row 0,
+// sums its 16 values per lane from zero and hands shift and sums to the lower wave through LDS (one barrier), which
+// continues with its 16 values, folds the two half-waves, corrects for the padding rows and writes the chunk.
+template <int STATS>
+__global__ __launch_bounds__(GR_BLOCK_T, 4) void gemm_rows_small_kernel(const float *__restrict__ A, const float *__restrict__ Bt,
+                                                                 int64_t M, int N, int K, int tiles_n, float *__restrict__ C,
+                                                                 float *__restrict__ partial, RowsEpilogue epi)
+{
+    constexpr int BT = 64;  // rows and columns of the workgroup tile
+    __shared__ __attribute__((aligned(16))) float sA[2][BT * GR_LD];
+    __shared__ __attribute__((aligned(16))) float sB[2][BT * GR_LD];
+    __shared__ float sStat[STATS ? 2 : 1][3][64];  // per wave column: shift, sum d, sum d^2 of the upper wave's lanes
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave >> 1, wc = wave & 1;
+    const int l31 = lane & 31, lh = lane >> 5;
+    const int ksteps = (K + GR_BK - 1) / GR_BK;
+    const int tail_groups = (K - (ksteps - 1) * GR_BK + 7) / 8;  // 8-wide k groups of the last step that hold columns
+
+    // Workgroup = (row block, 64-row half, 64-column tile).  The 4 * tiles_n workgroups of one 128-row block are 8 ids
+    // apart, i.e. on the same XCD (shared L2 for A), as the column tiles of a row block are in the 128 x 128 kernels.
+    const int per = 32 * tiles_n;
+    const int rem = (int)(blockIdx.x % per);
+    const int64_t rb = (int64_t)(blockIdx.x / per) * 8 + (rem & 7);
+    if (rb * GR_BM >= M) return;  // padding block (the grid covers whole groups of 8): no rows, no statistics
+    const int half = (rem >> 3) & 1;
+    const int n0 = (rem >> 4) * BT;
+    const int64_t m0 = rb * GR_BM + half * BT;
+
+    // staging: a tile is 64 rows x 32 k = 512 float4, 2 per thread and operand (rows frow and frow + 32)
+    const int frow = tid >> 3, fk4 = (tid & 7) * 4;
+    const bool oka0 = m0 + frow < M, oka1 = m0 + frow + 32 < M, okb0 = n0 + frow < N, okb1 = n0 + frow + 32 < N;
+    const float *pa0 = A + min(m0 + frow, M - 1) * K, *pa1 = A + min(m0 + frow + 32, M - 1) * K;
+    const float *pb0 = Bt + (size_t)min(n0 + frow, N - 1) * K, *pb1 = Bt + (size_t)min(n0 + frow + 32, N - 1) * K;
+    struct Stage {
+        float4 a0, a1, b0, b1;
+    };
+    auto fetch = [&](Stage &s, int k0) __attribute__((always_inline)) {
+        const int kk = min(k0 + fk4, K - 4);  // (K % 4 == 0: a float4 lies inside the row or past it)
+        s.a0 = *reinterpret_cast<const float4 *>(pa0 + kk);
+        s.a1 = *reinterpret_cast<const float4 *>(pa1 + kk);
+        s.b0 = *reinterpret_cast<const float4 *>(pb0 + kk);
+        s.b1 = *reinterpret_cast<const float4 *>(pb1 + kk);
+    };
+    // (a select of VALUES, component by component: `ok ? s.a0 : zero4` on the structs selects an address and keeps the
+    //  stages in scratch)
+    auto keep = [](bool ok, const float4 &v) __attribute__((always_inline)) {
+        return make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
+    };
+    auto stash = [&](const Stage &s, int buf, int k0) __attribute__((always_inline)) {
+        const bool kin = k0 + fk4 < K;  // rows past M and columns past N or K are staged as zeros
+        float *da = &sA[buf][frow * GR_LD + fk4], *db = &sB[buf][frow * GR_LD + fk4];
+        *reinterpret_cast<float4 *>(da) = keep(kin && oka0, s.a0);
+        *reinterpret_cast<float4 *>(da + 32 * GR_LD) = keep(kin && oka1, s.a1);
+        *reinterpret_cast<float4 *>(db) = keep(kin && okb0, s.b0);
+        *reinterpret_cast<float4 *>(db + 32 * GR_LD) = keep(kin && okb1, s.b1);
+    };
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+    auto compute = [&](int buf, int ng /*wave-uniform*/) __attribute__((always_inline)) {
+#pragma unroll
+        for (int g = 0; g < GR_BK / 8; ++g) {
+            if (g < ng) {
+                const float4 a = *reinterpret_cast<const float4 *>(&sA[buf][(wr * 32 + l31) * GR_LD + g * 8 + lh * 4]);
+                const float4 b = *reinterpret_cast<const float4 *>(&sB[buf][(wc * 32 + l31) * GR_LD + g * 8 + lh * 4]);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+            }
+        }
+    };
+
+    // Pairs of K-steps, then the odd last one (a single loop exit: both half-steps wait for their own stage only).  A
+    // buffer is rewritten two steps after it was read, behind the barrier of the step between.
+    Stage s0, s1;
+    fetch(s0, 0);
+    fetch(s1, GR_BK);
+    int ks = 0;
+#pragma unroll 1
+    for (; ks + 1 < ksteps; ks += 2) {
+        stash(s0, 0, ks * GR_BK);
+        fetch(s0, (ks + 2) * GR_BK);
+        __syncthreads();
+        compute(0, GR_BK / 8);
+        stash(s1, 1, (ks + 1) * GR_BK);
+        fetch(s1, (ks + 3) * GR_BK);
+        __syncthreads();
+        // last step of a contraction that is not a multiple of 32: only the 8-wide k groups that hold real columns
+        compute(1, ks + 2 < ksteps ? GR_BK / 8 : tail_groups);
+    }
+    if (ksteps & 1) {
+        stash(s0, 0, ks * GR_BK);
+        __syncthreads();
+        compute(0, tail_groups);
+    }
+
+    // ---- epilogue: D[row][col], col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+    const int n = n0 + wc * 32 + l31;
+    {
+        float emu = 0.0f, esc = 1.0f, ebe = 0.0f;
+        if (epi.mean && n < N) emu = epi.mean[n], esc = epi.scale[n], ebe = epi.beta[n];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int64_t m = m0 + wr * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+            float v = acc[e];
+            if (epi.mean) {  // (wave-uniform)
+                v = (v - emu) * esc + ebe;
+                v = v > 0.0f ? v : v * epi.slope;
+            }
+            if (m < M && n < N) C[m * N + n] = v;
+        }
+    }
+    if (STATS != 0) {
+        // shifted sums (d = v - K) as in gemm_rows_wide_kernel; rows past M were staged as zeros and are taken out again
+        const int valid = (int)min((int64_t)BT, max((int64_t)0, M - m0));  // workgroup-uniform
+        const float pad = (float)(BT - valid);
+        float k = 0.0f, s1 = 0.0f, s2 = 0.0f;
+        if (wr == 0) {
+            k = __shfl(acc[0], l31);  // first row of the 64
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const float d = acc[e] - k;
+                s1 += d;
+                s2 += d * d;
+            }
+            sStat[wc][0][lane] = k;
+            sStat[wc][1][lane] = s1;
+            sStat[wc][2][lane] = s2;
+        }
+        __syncthreads();
+        if (wr == 1) {
+            k = sStat[wc][0][lane];
+            s1 = sStat[wc][1][lane];
+            s2 = sStat[wc][2][lane];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const float d = acc[e] - k;
+                s1 += d;
+                s2 += d * d;
+            }
+            s1 += __shfl_xor(s1, 32);  // the two half-waves hold different rows of the same column
+            s2 += __shfl_xor(s2, 32);
+            s1 += pad * k;
+            s2 -= pad * (k * k);
+            if (lh == 0 && n < N) {
+                float *pr = partial + ((size_t)(rb * 2 + half) * 4) * N + n;
+                pr[0] = s1;
+                pr[(size_t)N] = s2;
+                pr[(size_t)2 * N] = k;
+                pr[(size_t)3 * N] = (float)valid;
+            }
+        }
+    }
+}
 
 // out[e] = sum_s slab[s][e], s ascending (fixed order => reproducible); one float4 per thread
 __global__ __launch_bounds__(256) void gemm_rows_sum_slabs_kernel(const float *__restrict__ slabs, int S, int64_t MN4,
@@ -475,52 +642,20 @@ __global__ __launch_bounds__(256) void gemm_rows_sum_slabs_kernel(const float *_
 using namespace tp3d;
 
 namespace {
-constexpr int GR_GRID = 1024;  // persistent: 4 workgroups per CU, a multiple of 8
-struct RowsPlan {
-    bool wide;  // 128 x 128 tiles (else 128 x 64)
-    int tiles_n, wave_rows;
-    int64_t row_blocks, items, blocks;
-    bool per_workgroup;  // statistics chunks: per (workgroup, wave row) instead of per (128-row block, wave row)
-    int64_t chunks;
-    int ksplit, kchunk;  // K-ranges of a split launch (1 = no split)
-};
-RowsPlan rows_plan(int64_t M, int N, int K = 0, bool allow_split = false)
-{
-    RowsPlan p;
-    // narrow tiles when they cover N with less padding (N <= 64, or a remainder of at most 64 columns: 192, 320 ...)
-    const int rem = N % 128;
-    p.wide = !(rem > 0 && rem <= 64);
-    const int bn = p.wide ? 128 : 64;
-    p.wave_rows = p.wide ? 2 : 4;
-    p.tiles_n = (N + bn - 1) / bn;
-    p.row_blocks = (M + GR_BM - 1) / GR_BM;
-    const int64_t groups = (p.row_blocks + 7) / 8;
-    p.items = groups * 8 * p.tiles_n;  // items past the last row block stage zeros and store nothing
-    p.blocks = p.items < GR_GRID ? p.items : GR_GRID;
-    p.per_workgroup = p.blocks == GR_GRID && GR_GRID % (8 * p.tiles_n) == 0;
-    p.chunks = p.wave_rows * (p.per_workgroup ? GR_GRID / p.tiles_n : p.row_blocks);
-    p.ksplit = 1;
-    p.kchunk = K > 0 ? (K + GR_BK - 1) / GR_BK * GR_BK : 0;
-    if (allow_split && K >= 1024 && p.items <= 128) {
-        // few output tiles and a very long contraction (the 1280 / 1536-channel decoder layers): K-ranges of >= 128
-        // (every range writes an M x N slab that the summing pass reads back, so no more ranges than needed)
-        const int want = (int)((512 + p.items - 1) / p.items);
-        const int by_k = K / 128;
-        int s = want < by_k ? want : by_k;
-        if (s > 16) s = 16;
-        if (s > 1) {
-            p.kchunk = ((K + s - 1) / s + GR_BK - 1) / GR_BK * GR_BK;
-            p.ksplit = (K + p.kchunk - 1) / p.kchunk;
-        }
-    }
-    return p;
-}
-
+// (RowsPlan / rows_plan / rows_small_plan: gemm_plans.h)
 template <bool WIDE>
 int launch_rows(const RowsPlan &p, const float *A, const float *Bt, int64_t M, int N, int K, float *C, float *stat_partial,
                 const RowsEpilogue &epi, hipStream_t s)
 {
     const dim3 grid((unsigned)p.blocks, (unsigned)p.ksplit), block(GR_BLOCK_T);
+    if (const RowsSmallPlan sp = rows_small_plan(p); WIDE && sp.routed) {  // few rows: 64 x 64 tiles, four times the workgroups
+        const dim3 sgrid((unsigned)sp.blocks);
+        if (stat_partial)
+            hipLaunchKernelGGL(gemm_rows_small_kernel<1>, sgrid, block, 0, s, A, Bt, M, N, K, p.tiles_n, C, stat_partial, epi);
+        else
+            hipLaunchKernelGGL(gemm_rows_small_kernel<0>, sgrid, block, 0, s, A, Bt, M, N, K, p.tiles_n, C, stat_partial, epi);
+        return check_launch();
+    }
     if (WIDE && p.ksplit == 1) {  // the dedicated plain 128 x 128 kernel
         if (stat_partial && p.per_workgroup)
             hipLaunchKernelGGL(gemm_rows_wide_kernel<2>, grid, block, 0, s, A, Bt, M, N, K, p.tiles_n, p.items, C, stat_partial, epi);
@@ -606,6 +741,29 @@ TP3D_EXPORT int tp3d_gemm_rows_plan(int64_t M, int N, int K, int64_t *plan)
     plan[6] = p.wave_rows;
     plan[7] = p.ksplit;
     plan[8] = p.wide ? 128 : 64;
+    return TP3D_OK;
+}
+
+// 1 (the default): few-row launches of tp3d_gemm_rows_f32 / _epi_f32 and tp3d_gemm_tn_f32 take the smaller workgroup tiles
+// of gemm_plans.h; 0: the plans without that rule.  Same results either way.  Process-wide: set it before sizes are
+// queried and before a step is captured into a graph.
+TP3D_EXPORT int tp3d_set_few_row_tiles(int on)
+{
+    g_few_row_tiles = on != 0;
+    return TP3D_OK;
+}
+
+// plan[0..3] = 64 x 64 work items, workgroups (one per item, at most 1024), 1 when the launch WITH statistics (never
+// K-split) takes the 64 x 64 form, 1 when the launch without statistics does (K-split where tp3d_gemm_rows_plan says so);
+// items and workgroups are 0 when neither does
+TP3D_EXPORT int tp3d_gemm_rows_small_plan(int64_t M, int N, int K, int64_t *plan)
+{
+    if (M <= 0 || N <= 0 || K < 0 || !plan) return TP3D_E_BADARG;
+    const RowsSmallPlan a = rows_small_plan(rows_plan(M, N, K, false)), b = rows_small_plan(rows_plan(M, N, K, K > 0));
+    plan[0] = a.routed ? a.items : b.items;
+    plan[1] = a.routed ? a.blocks : b.blocks;
+    plan[2] = a.routed ? 1 : 0;
+    plan[3] = b.routed ? 1 : 0;
     return TP3D_OK;
 }
 

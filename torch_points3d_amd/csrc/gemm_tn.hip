@@ -14,6 +14,7 @@
 // (torch_points3d/core/common_modules/dense_modules.py:5-12,25-29) -- computed by autograd in the reference.
 #include <type_traits>
 
+#include "gemm_plans.h"
 #include "tp3d_common.h"
 
 namespace tp3d {
@@ -21,7 +22,6 @@ namespace tp3d {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int TN_BLOCK = 256;  // 4 waves as 2 x 2
-constexpr int TN_BR_MAX = 64;  // most rows staged per step (narrow tiles stage more rows per barrier)
 
 // Each wave owns WM x WN MFMA tiles of 32x32; the four waves form a GN x (4/GN) grid, so the workgroup tile is
 // (GN*WM*32) x ((4/GN)*WN*32): 2 x 2 waves normally, 1 x 4 for a handful of output rows (the class-score layer: N = 10
@@ -169,45 +169,7 @@ int tn_reduce_splits(const float *partial, int splits, int64_t NK, float *out, h
     return check_launch();
 }
 
-struct TnPlan {
-    int wm, wn, gn, tn, tk, tiles_n, tiles_k, splits;
-    int64_t rows_per_split;
-};
-
-static TnPlan plan_tn(int64_t M, int N, int K)
-{
-    TnPlan p;
-    p.wm = N > 64 ? 2 : 1;
-    // K just above a multiple of 128 (131 = 128 features + xyz): 192-wide tiles halve the padded columns and read dY
-    // once instead of twice; wider K: 192 only where it strictly removes padded columns
-    if (K <= 64) p.wn = 1;
-    else if (K <= 128) p.wn = 2;
-    else if (K <= 192) p.wn = 3;
-    else p.wn = ((K + 191) / 192) * 192 < ((K + 127) / 128) * 128 ? 3 : 2;
-    p.gn = 2;
-    if (N <= 32 && K >= 128) {  // a handful of output rows: one wave row, four wave columns (32 x 128 tiles)
-        p.gn = 1;
-        p.wm = 1;
-        p.wn = 1;
-    }
-    p.tn = 32 * p.gn * p.wm;
-    p.tk = 32 * (4 / p.gn) * p.wn;
-    p.tiles_n = (N + p.tn - 1) / p.tn;
-    p.tiles_k = (K + p.tk - 1) / p.tk;
-    const int tiles = p.tiles_n * p.tiles_k;
-    // ~4 workgroups per CU (256 CUs) keep the MFMA pipes fed; at least 256 rows per split, at most 512 splits
-    // (every split writes an N x K partial tile that the reduction pass reads back)
-    int64_t want = (1024 + tiles - 1) / tiles;
-    const int min_rows = 256;
-    int64_t max_by_rows = (M + min_rows - 1) / min_rows;
-    int64_t s = want < max_by_rows ? want : max_by_rows;
-    if (s < 1) s = 1;
-    if (s > 512) s = 512;
-    p.rows_per_split = ((M + s - 1) / s + TN_BR_MAX - 1) / TN_BR_MAX * TN_BR_MAX;
-    p.splits = (int)((M + p.rows_per_split - 1) / p.rows_per_split);
-    return p;
-}
-
+// (TnPlan / plan_tn: gemm_plans.h)
 static int launch_tn(const float *dY, const float *A, int64_t M, int N, int K, float *out, float *workspace, hipStream_t s)
 {
     const TnPlan p = plan_tn(M, N, K);

@@ -165,6 +165,7 @@ def _gemm_tn_launch(kernel, dY, A, terms, act, reverse):
             _lib.call("tp3d_gemm_tn_x3_f32", _lib.ptr(dY), _lib.ptr(A), M, N, K, int(terms), _lib.ptr(out), _lib.ptr(ws), int(reverse),
                       _lib.stream_ptr(dev))
         else:
+            sync_few_row_tiles()
             _lib.call("tp3d_gemm_tn_f32", _lib.ptr(dY), _lib.ptr(A), M, N, K, _lib.ptr(out), _lib.ptr(ws),
                       _lib.stream_ptr(dev))
     return out
@@ -201,6 +202,7 @@ def gemm_rows(A, Bt, want_stats=False):
     C = torch.empty((M, N), dtype=torch.float32, device=dev)
     part, slabs = None, None
     h = _lib.load()
+    sync_few_row_tiles()
     if want_stats:
         part = _lib.workspace("gemm_rows_stats", 4 * h.tp3d_gemm_rows_stat_floats(M, N), dev)
     else:
@@ -249,6 +251,23 @@ def eval_state_key(tensors, bns):
     without moving a version counter -- the training passes of every BatchNorm in `bns` and the replay count."""
     return (tuple((t.data_ptr(), t._version) for t in tensors)
             + tuple(getattr(bn, "_tp3d_train_passes", 0) for bn in bns) + (_replay_epoch,))
+
+
+FEW_ROW_TILES = 1  # 1: few-row launches (4096 / 16384 rows) of the plain rows GEMM and the fp32 weight-gradient GEMM run on
+                   # quarter- / half-size workgroup tiles so that they fill the CUs (csrc/gemm_plans.h); 0: the 128 x 128
+                   # plans.  Bit-identical results.  A process-wide setting of the library: with a captured step, fix it
+                   # before warm-up
+_few_row_pushed = None
+
+
+def sync_few_row_tiles():
+    """hand FEW_ROW_TILES to the library when it has changed (tp3d_set_few_row_tiles) -- in front of every launch and plan
+    query it bears on, so that `bench.py --set FEW_ROW_TILES=0` and the tests switch routes within one process"""
+    global _few_row_pushed
+    v = int(FEW_ROW_TILES)
+    if v != _few_row_pushed:
+        _lib.load().tp3d_set_few_row_tiles(v)
+        _few_row_pushed = v
 
 
 ROWS_GEMM_MIN_COLS = 32   # narrower outputs (class scores, edge MLPs) stay on the library / skinny kernels
@@ -382,6 +401,7 @@ class _LinearBNAct(torch.autograd.Function):
                     _lib.call("tp3d_gemm_skinny_bnact_f32", _lib.ptr(A), _lib.ptr(W2.contiguous()), M, Cout, Kp, Kp,
                               _lib.ptr(stats[0]), _lib.ptr(stats[2]), _lib.ptr(stats[3]), slope, _lib.ptr(out), st)
                 else:
+                    sync_few_row_tiles()
                     n = _lib.load().tp3d_gemm_rows_workspace_floats(M, Cout, Kp)
                     slabs = _lib.workspace("gemm_rows_slabs", 4 * n, dev) if n else None
                     _lib.call("tp3d_gemm_rows_epi_f32", _lib.ptr(A), _lib.ptr(W2.contiguous()), M, Cout, Kp, _lib.ptr(stats[0]),
@@ -491,6 +511,7 @@ class _MLPChain(torch.autograd.Function):
                     if l:  # a width the split-role kernel does not serve: the separate pass, then the plain rows GEMM
                         src = _bn_act_out(Ys[-1], stats[-1], layers[l - 1][1], 0, st)[0]
                         acts[l - 1] = src if p.keep_act else None
+                    sync_few_row_tiles()
                     _lib.call("tp3d_gemm_rows_f32", _lib.ptr(src), _lib.ptr(W2), M, Cout, Kp, _lib.ptr(Y), _lib.ptr(part), None, st)
                 else:
                     if l == 0:
