@@ -826,6 +826,58 @@ int tp3d_box_best_gt_f64(const float *det_corners, const int64_t *det_class, con
 int tp3d_ap_match(const int64_t *order, const int64_t *det_class, const int64_t *det_scene, int64_t D, const double *ovmax,
                   const int64_t *jmax, int64_t G, const double *thresholds, int T, uint8_t *taken, uint8_t *tp, void *stream);
 
+/* Segmentation metrics (csrc/seg_metrics.hip)
+ *                       [metrics/confusion_matrix.py, segmentation_tracker.py, shapenet_part_tracker.py, s3dis_tracker.py,
+ *                        segmentation_helpers.py]
+ * Integer counters only: no float arithmetic in the counting kernels, no float atomics anywhere, results independent of
+ * the launch geometry.  Nothing is read back and nothing of the size of the input is written.
+ *   Row argmax (confusion and part counts): the prediction of a row is the LOWEST column holding the row's maximum over
+ *     the given column range (numpy's argmax); the running maximum starts from the first column of the range, so rows
+ *     of negative log-probabilities are served.  Rows holding NaN are outside the contract (the library is built with
+ *     -fno-honor-nans): their prediction is unspecified, though always inside the range.
+ *   tp3d_confusion_count_f32: cm is int64 (C * C + 1), ACCUMULATED into and never cleared here.  Row i of N:
+ *       labels[i] == ignore_label: skipped (pass INT64_MIN for "no ignore label");
+ *       row_index given and row_index[i] == -1: skipped; otherwise the scores row is row_index[i] (i without row_index);
+ *       a label outside [0, C), a scores row outside [0, n_score_rows) or (pred mode) a prediction outside [0, C):
+ *         cm[C * C] += 1, the "invalid" counter, and no matrix cell changes;
+ *       else cm[label * C + prediction] += 1, prediction = col_lo + argmax of scores[row, col_lo .. col_hi), or pred[i].
+ *     scores (n_score_rows, >= col_hi) fp32 with row stride ld >= col_hi, 0 <= col_lo < col_hi <= C; or scores = NULL and
+ *     pred (N) int64 (then row_index must be NULL and ld, col_lo, col_hi are not read).  Rows are staged through LDS in
+ *     tiles of tp3d_confusion_tile_rows() with coalesced loads, then one lane per row.  For
+ *     C <= TP3D_CONFUSION_LDS_MAX_CLASSES a workgroup counts in C * C int32 LDS cells and adds its non-zero cells to cm
+ *     once, with agent-scope 64-bit integer atomics; wider matrices are counted with those atomics directly.
+ *     N <= 2^40 (TP3D_E_TOOBIG beyond).
+ *   tp3d_part_iou_counts_f32 (ShapeNet protocol): B clouds, cloud b = rows seg[b] .. seg[b + 1]) of scores (N, C), row
+ *     stride ld >= C, and labels (N).  part_lo[C], part_hi[C] (int32, device): for every label the range [lo, hi) of the
+ *     labels of its category.  One workgroup per cloud.  The category is that of the cloud's FIRST label; a row's
+ *     prediction is lo + argmax over columns [lo, hi) only.  counts (B, TP3D_PART_IOU_MAX_PARTS, 2) int32 =
+ *     (intersection, union) of label == part and prediction == part for part = lo + p, zero for p >= hi - lo; a label
+ *     outside [lo, hi) matches no part.  cat_lo (B) int32 = lo, -1 for an empty cloud, -2 (and zero counts) where the
+ *     first label is outside [0, C), the tables give an empty, out-of-range or too wide category, or seg is not ascending
+ *     inside [0, N].  max_parts = the widest category of the tables as the caller knows it:
+ *     > TP3D_PART_IOU_MAX_PARTS is TP3D_E_TOOBIG.  "Absent part counts as 1" and the means are the host's.
+ *   tp3d_vote_add_f32: votes[ids[i], :] += out[i, :], counts[ids[i]] += 1 for the n rows of out (n, C), row stride ld.
+ *     votes (T, C) fp32 contiguous, counts (T) int32, workspace (T) int64 zeroed ONCE when allocated and then owned by
+ *     these votes, errors (1) int64: += 1 per id outside [0, T) (that row adds nothing).  epoch: 1, 2, 3, ... one more
+ *     per call on the same workspace (< 2^31).  With unique ids the result is bit-equal to the indexed add.  Duplicate
+ *     rule: of the rows of ONE call naming the same target, only the one with the HIGHEST row index is added, and the
+ *     count rises by one.  Pass 1 takes the integer maximum of (epoch << 32 | row) per target, so a word left by an
+ *     earlier call never wins and nothing of size T is cleared; pass 2 lets the winning rows write with plain stores.
+ *     n <= 2^31 - 1. */
+#define TP3D_CONFUSION_LDS_MAX_CLASSES 80
+#define TP3D_PART_IOU_MAX_PARTS 16
+int tp3d_confusion_tile_rows(void);
+int tp3d_confusion_lds_max_classes(void);
+int tp3d_part_iou_max_parts(void);
+int tp3d_confusion_count_f32(const float *scores, int64_t n_score_rows, int ld, const int64_t *pred, const int64_t *labels,
+                             const int64_t *row_index, int64_t N, int C, int col_lo, int col_hi, int64_t ignore_label,
+                             int64_t *cm, void *stream);
+int tp3d_part_iou_counts_f32(const float *scores, int ld, const int64_t *labels, const int64_t *seg, int64_t N, int64_t B, int C,
+                             const int32_t *part_lo, const int32_t *part_hi, int max_parts, int32_t *counts, int32_t *cat_lo,
+                             void *stream);
+int tp3d_vote_add_f32(const float *out, int ld, const int64_t *ids, int64_t n, int C, int64_t T, int64_t epoch, float *votes,
+                      int32_t *counts, int64_t *workspace, int64_t *errors, void *stream);
+
 /* =====================================================================================================
  * Launch plans (host arithmetic only, no device work): what an entry point WILL do for given sizes -- how it
  * splits the rows, how many partial rows it writes, how it carves its workspace.  tests/test_plans_cpu.py sweeps

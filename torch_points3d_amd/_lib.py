@@ -112,6 +112,9 @@ SIGNATURES = {
     "tp3d_box3d_iou_f64": [_p, _p, _l, _l, _p, _p],
     "tp3d_box_best_gt_f64": [_p, _p, _p, _l, _p, _p, _p, _l, _l, _p, _p, _p],
     "tp3d_ap_match": [_p, _p, _p, _l, _p, _p, _l, _p, _i, _p, _p, _p],
+    "tp3d_confusion_count_f32": [_p, _l, _i, _p, _p, _p, _l, _i, _i, _i, _l, _p, _p],
+    "tp3d_part_iou_counts_f32": [_p, _i, _p, _p, _l, _l, _i, _p, _p, _i, _p, _p, _p],
+    "tp3d_vote_add_f32": [_p, _i, _p, _l, _i, _l, _l, _p, _p, _p, _p, _p],
     # launch plans (host arithmetic; the last argument is a HOST int64 array)
     "tp3d_gemm_tn_plan": [_l, _i, _i, _p],
     "tp3d_gemm_tn_x3_plan": [_l, _i, _i, _p],
@@ -163,6 +166,9 @@ MISC = {
     "tp3d_segment_transform_wgrad_workspace_bytes": (_z, [_l, _l, _i]),
     "tp3d_segment_sum_workspace_bytes": (_z, [_l, _l, _i]),
     "tp3d_box_nms_max_boxes": (_i, []),
+    "tp3d_confusion_tile_rows": (_i, []),
+    "tp3d_confusion_lds_max_classes": (_i, []),
+    "tp3d_part_iou_max_parts": (_i, []),
 }
 ABI_VERSION = 39
 

@@ -1318,3 +1318,115 @@ def ap_match(det_corners, det_score, det_class, det_scene, gt_corners, gt_class,
             _lib.call("tp3d_ap_match", _lib.ptr(order), _lib.ptr(det_class), _lib.ptr(det_scene), D, _lib.ptr(ovmax),
                       _lib.ptr(jmax), G, _lib.ptr(thr), T, _lib.ptr(taken), _lib.ptr(tp), _lib.stream_ptr(dev))
     return tp.bool(), ovmax, jmax
+
+
+NO_IGNORE_LABEL = -(1 << 63)  # the "no ignore label" value of tp3d_confusion_count_f32
+
+
+def _label_vector(t, name, n=None):
+    if t.dim() != 1 or (n is not None and t.numel() != n):
+        raise ValueError("%s must be a vector%s, got %s" % (name, "" if n is None else " of %d entries" % n, tuple(t.shape)))
+    return _i64(t)
+
+
+def confusion_count(cm, labels, scores=None, pred=None, ignore_label=None, row_index=None, columns=None):
+    """Adds the rows of one batch to the confusion counts `cm` (int64, C * C + 1, on the device; row-major
+    [label, prediction], the last entry counting invalid rows) in one launch; returns cm.  Either `scores` (n, >= C)
+    fp32, whose rows may be a column slice of a wider tensor, the prediction being the first maximum of the row over
+    `columns` = (lo, hi), default (0, C); or `pred` (N) int64.  `row_index` (N): row i reads scores[row_index[i]], -1
+    skips the row.  Rows whose label is `ignore_label` are skipped; a label (or prediction, or scores row) out of range
+    counts as invalid and changes no cell.  Nothing is read back.  Device tensors only."""
+    if cm.dim() != 1 or cm.dtype != torch.int64 or not cm.is_contiguous():
+        raise ValueError("cm must be a contiguous int64 vector of C * C + 1 entries")
+    C = int(round((cm.numel() - 1) ** 0.5))
+    if C < 1 or C * C + 1 != cm.numel():
+        raise ValueError("cm must have C * C + 1 entries, got %d" % cm.numel())
+    if (scores is None) == (pred is None):
+        raise ValueError("exactly one of scores and pred is needed")
+    dev = _dev(cm, labels, scores, pred, row_index)
+    labels = _label_vector(labels, "labels")
+    N = labels.numel()
+    ign = NO_IGNORE_LABEL if ignore_label is None else int(ignore_label)
+    if pred is not None:
+        if row_index is not None or columns is not None:
+            raise ValueError("row_index and columns go with scores, not with pred")
+        pred = _label_vector(pred, "pred", N)
+        args = (None, 0, 0, _lib.ptr(pred), _lib.ptr(labels), None, N, C, 0, 0)
+    else:
+        if scores.dim() != 2:
+            raise ValueError("scores must be (n, C), got %s" % (tuple(scores.shape),))
+        lo, hi = (0, C) if columns is None else (int(columns[0]), int(columns[1]))
+        if not (0 <= lo < hi <= C) or scores.shape[1] < hi:
+            raise ValueError("columns (%d, %d) must lie inside the %d classes and the %d score columns"
+                             % (lo, hi, C, scores.shape[1]))
+        scores, ld = _rows_ld(scores)
+        if row_index is None:
+            if scores.shape[0] != N:
+                raise ValueError("scores has %d rows for %d labels" % (scores.shape[0], N))
+        else:
+            row_index = _label_vector(row_index, "row_index", N)
+        args = (_lib.ptr(scores), scores.shape[0], ld, None, _lib.ptr(labels), _lib.ptr(row_index), N, C, lo, hi)
+    if N:
+        with _lib.on_device(dev):
+            _lib.call("tp3d_confusion_count_f32", *args, ign, _lib.ptr(cm), _lib.stream_ptr(dev))
+    return cm
+
+
+PART_IOU_MAX_PARTS = 16  # TP3D_PART_IOU_MAX_PARTS of include/tp3d_hip.h
+
+
+def part_iou_counts(scores, labels, seg, part_lo, part_hi, max_parts):
+    """ShapeNet part counts of B clouds in one launch, one workgroup per cloud: scores (N, C) fp32, labels (N), cloud
+    offsets seg (B + 1), part_lo / part_hi (C) int32: the label range [lo, hi) of every label's category.  The category
+    of a cloud is that of its first label and a row's prediction the first maximum over columns [lo, hi).  Returns
+    (counts (B, PART_IOU_MAX_PARTS, 2) int32 = (intersection, union) per part, cat_lo (B) int32: the category's first
+    label, -1 for an empty cloud, -2 for a cloud whose first label or category is unusable).  `max_parts` is the widest
+    category of the tables.  Nothing is read back.  Device tensors only."""
+    dev = _dev(scores, labels, seg, part_lo, part_hi)
+    if scores.dim() != 2:
+        raise ValueError("scores must be (N, C), got %s" % (tuple(scores.shape),))
+    N, C = scores.shape
+    labels = _label_vector(labels, "labels", N)
+    seg = _label_vector(seg, "seg")
+    if seg.numel() < 1:
+        raise ValueError("seg must be (B + 1,)")
+    B = seg.numel() - 1
+    if part_lo.dtype != torch.int32 or part_hi.dtype != torch.int32 or tuple(part_lo.shape) != (C,) \
+            or tuple(part_hi.shape) != (C,):
+        raise ValueError("part_lo and part_hi must be int32 vectors of C = %d entries" % C)
+    if C < 1 or int(max_parts) < 1:
+        raise ValueError("at least one class and one part are needed")
+    scores, ld = _rows_ld(scores)
+    counts = torch.empty((B, PART_IOU_MAX_PARTS, 2), dtype=torch.int32, device=dev)
+    cat_lo = torch.empty((B,), dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_part_iou_counts_f32", _lib.ptr(scores), ld, _lib.ptr(labels), _lib.ptr(seg), N, B, C,
+                  _lib.ptr(part_lo.contiguous()), _lib.ptr(part_hi.contiguous()), int(max_parts), _lib.ptr(counts),
+                  _lib.ptr(cat_lo), _lib.stream_ptr(dev))
+    return counts, cat_lo
+
+
+def vote_add(votes, counts, workspace, errors, epoch, ids, out):
+    """votes[ids] += out; counts[ids] += 1 on the device (s3dis_tracker.py:56-57, segmentation_helpers.py:71-73) without
+    float atomics.  votes (T, C) fp32, counts (T) int32, workspace (T) int64 zeroed when allocated and kept with these
+    votes, errors (1) int64 counting ids outside [0, T), epoch = 1, 2, ... one more per call.  With unique ids the
+    result is bit-equal to the torch statement; of several rows of one call with the same id the one with the HIGHEST
+    row index is added and the count rises by one (torch leaves that case undefined).  Nothing is read back."""
+    dev = _dev(votes, counts, workspace, errors, ids, out)
+    if votes.dim() != 2 or votes.dtype != torch.float32 or not votes.is_contiguous():
+        raise ValueError("votes must be a contiguous (T, C) fp32 tensor")
+    T, C = votes.shape
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (T,) or workspace.dtype != torch.int64 \
+            or tuple(workspace.shape) != (T,) or errors.dtype != torch.int64 or errors.numel() != 1:
+        raise ValueError("counts (T) int32, workspace (T) int64 and errors (1) int64 must match votes")
+    ids = _label_vector(ids, "ids")
+    n = ids.numel()
+    if out.dim() != 2 or tuple(out.shape) != (n, C):
+        raise ValueError("out must be (%d, %d), got %s" % (n, C, tuple(out.shape)))
+    if C < 1 or not (0 < int(epoch) < (1 << 31)):
+        raise ValueError("votes need at least one class and an epoch in [1, 2^31)")
+    out, ld = _rows_ld(out)
+    if n:
+        with _lib.on_device(dev):
+            _lib.call("tp3d_vote_add_f32", _lib.ptr(out), ld, _lib.ptr(ids), n, C, T, int(epoch), _lib.ptr(votes),
+                      _lib.ptr(counts), _lib.ptr(workspace), _lib.ptr(errors), _lib.stream_ptr(dev))
