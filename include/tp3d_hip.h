@@ -878,6 +878,57 @@ int tp3d_part_iou_counts_f32(const float *scores, int ld, const int64_t *labels,
 int tp3d_vote_add_f32(const float *out, int ld, const int64_t *ids, int64_t n, int C, int64_t T, int64_t epoch, float *votes,
                       int32_t *counts, int64_t *workspace, int64_t *errors, void *stream);
 
+/* Panoptic metrics (csrc/panoptic_metrics.hip)
+ *                       [metrics/panoptic_tracker.py, models/panoptic/structures.py:6-49]
+ * Clusters are a CSR: cluster k owns members[starts[k] .. starts[k + 1]) (point indices), member_cluster[e] = the cluster
+ * of slot e (ascending).  Integer counters only, no float atomics, bit-equal repeats, nothing read back; memory is
+ * proportional to the slots M, the clusters K, the instances G and the overlapping cluster pairs -- there is no (K, N),
+ * (K, K) or (K, G) array.  K, M and the pair capacity are at most 2^31 - 1 (TP3D_E_TOOBIG beyond).
+ *   tp3d_cluster_best_instance: column (N) = the ground-truth column of every point or -1; gt_size, gt_class (G);
+ *     cluster_class, col_lo, col_hi (K): the columns [col_lo, col_hi) of the cluster's cloud (members with a column
+ *     outside it are not counted).  One workgroup per cluster (one wave up to 256 members) counts the members per column
+ *     in an LDS histogram of TP3D_CLUSTER_BEST_WINDOW columns, window after window.  With n = the cluster's slots:
+ *       inter_all, col_all: the first maximum over the columns with inter > 0 of the fp32 value
+ *         fp32(inter) / max((fp32(n) + fp32(gt_size)) - fp32(inter), 1), one rounding per operation; col_all = -1 and
+ *         inter_all = 0 when no column has a member;
+ *       inter_cls, col_cls: the first maximum over the columns with inter > 0 and gt_class == cluster_class of the
+ *         float64 value inter / (n + gt_size - inter); -1 and 0 without such a column.
+ *   Sparse overlaps, two calls that share `stats` (3 int64, device) and the count workspace:
+ *     tp3d_cluster_overlap_count sorts the slots by point (stable, over the low point_bits bits: members in
+ *       [0, 2^point_bits)) and counts, per slot, the other clusters that hold its point (a cluster that lists a point
+ *       twice counts once); stats[0] = the number Q of ordered (cluster, other) pairs over all points, stats[1..2] = 0.
+ *     tp3d_cluster_overlap_emit writes those pairs as keys cluster * K + other into `cap` slots, sorts them and reduces
+ *       the runs: ov_start (K + 1), ov_other and ov_inter (cap; the first ov_start[K] entries are written): for cluster
+ *       k the entries ov_start[k] .. ov_start[k + 1]) list the clusters it shares a point with, ascending, and the number
+ *       of shared points; both directions are stored.  stats[1] = ov_start[K].  Q > cap: stats[2] = 1, ov_start is all
+ *       zero and the entries are unspecified (nothing is written outside the buffers).
+ *   tp3d_cluster_nms: order (K) = the visiting order (the host wrapper sorts); hot, keep (K) bytes.  A cluster that is
+ *     alive when visited clears every neighbour j with fp32(inter) / ((fp32(n_i) + fp32(n_j)) - fp32(inter)) > threshold.
+ *     Clusters without such a neighbour (hot = 0) are kept by a parallel pass; one workgroup walks the others in order,
+ *     its lanes spread over the neighbour list of the visited cluster.  P = the entries of ov_other / ov_inter.
+ *   tp3d_instance_ap_match: the sibling of tp3d_ap_match for instances.  order (K) lists the clusters grouped by (cloud,
+ *     class), inside a group in visiting order.  tp[d] = 1 when valid[d], col_cls[d] >= 0, the float64 IoU
+ *     inter_cls / (size + gt_size[col_cls] - inter_cls) >= threshold (not strict) and the instance has not been taken by
+ *     an earlier cluster of the group.  taken (G) bytes of scratch (cleared here); tp (K) bytes, written for every d. */
+#define TP3D_CLUSTER_BEST_WINDOW 1024
+int tp3d_cluster_best_window(void);
+int tp3d_cluster_best_instance(const int64_t *members, const int64_t *starts, int64_t M, int64_t K, const int64_t *column,
+                               int64_t N, const int64_t *gt_size, const int64_t *gt_class, int64_t G,
+                               const int64_t *cluster_class, const int64_t *col_lo, const int64_t *col_hi, int64_t *inter_all,
+                               int64_t *col_all, int64_t *inter_cls, int64_t *col_cls, void *stream);
+size_t tp3d_cluster_overlap_count_workspace_bytes(int64_t M);
+size_t tp3d_cluster_overlap_emit_workspace_bytes(int64_t cap);
+int tp3d_cluster_overlap_count(const int64_t *members, const int64_t *member_cluster, int64_t M, int64_t K, int point_bits,
+                               int64_t *stats, void *workspace, size_t workspace_bytes, void *stream);
+int tp3d_cluster_overlap_emit(const int64_t *member_cluster, int64_t M, int64_t K, int64_t cap, int64_t *ov_start,
+                              int64_t *ov_other, int64_t *ov_inter, int64_t *stats, void *count_workspace,
+                              size_t count_workspace_bytes, void *workspace, size_t workspace_bytes, void *stream);
+int tp3d_cluster_nms(const int64_t *order, const int64_t *starts, int64_t K, const int64_t *ov_start, const int64_t *ov_other,
+                     const int64_t *ov_inter, int64_t P, float threshold, uint8_t *hot, uint8_t *keep, void *stream);
+int tp3d_instance_ap_match(const int64_t *order, const int64_t *cls, const int64_t *cloud, const uint8_t *valid, int64_t K,
+                           const int64_t *size, const int64_t *inter_cls, const int64_t *col_cls, const int64_t *gt_size,
+                           int64_t G, double threshold, uint8_t *taken, uint8_t *tp, void *stream);
+
 /* =====================================================================================================
  * Launch plans (host arithmetic only, no device work): what an entry point WILL do for given sizes -- how it
  * splits the rows, how many partial rows it writes, how it carves its workspace.  tests/test_plans_cpu.py sweeps

@@ -115,6 +115,11 @@ SIGNATURES = {
     "tp3d_confusion_count_f32": [_p, _l, _i, _p, _p, _p, _l, _i, _i, _i, _l, _p, _p],
     "tp3d_part_iou_counts_f32": [_p, _i, _p, _p, _l, _l, _i, _p, _p, _i, _p, _p, _p],
     "tp3d_vote_add_f32": [_p, _i, _p, _l, _i, _l, _l, _p, _p, _p, _p, _p],
+    "tp3d_cluster_best_instance": [_p, _p, _l, _l, _p, _l, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p],
+    "tp3d_cluster_overlap_count": [_p, _p, _l, _l, _i, _p, _p, ctypes.c_size_t, _p],
+    "tp3d_cluster_overlap_emit": [_p, _l, _l, _l, _p, _p, _p, _p, _p, ctypes.c_size_t, _p, ctypes.c_size_t, _p],
+    "tp3d_cluster_nms": [_p, _p, _l, _p, _p, _p, _l, _f, _p, _p, _p],
+    "tp3d_instance_ap_match": [_p, _p, _p, _p, _l, _p, _p, _p, _p, _l, ctypes.c_double, _p, _p, _p],
     # launch plans (host arithmetic; the last argument is a HOST int64 array)
     "tp3d_gemm_tn_plan": [_l, _i, _i, _p],
     "tp3d_gemm_tn_x3_plan": [_l, _i, _i, _p],
@@ -169,6 +174,9 @@ MISC = {
     "tp3d_confusion_tile_rows": (_i, []),
     "tp3d_confusion_lds_max_classes": (_i, []),
     "tp3d_part_iou_max_parts": (_i, []),
+    "tp3d_cluster_best_window": (_i, []),
+    "tp3d_cluster_overlap_count_workspace_bytes": (_z, [_l]),
+    "tp3d_cluster_overlap_emit_workspace_bytes": (_z, [_l]),
 }
 ABI_VERSION = 39
 

@@ -14,8 +14,9 @@ loop and no dense (clusters, N) mask.
 Served: every scorer_type -- "MLP" and None as they stand, "unet" and "encoder" (a sparse network over one cloud per cluster:
 torchpoints.cluster_voxelize builds the tensor, SparseTensor(clouds=K) holds more than 2^9 clouds) when the scorer's config
 is handed in (`scorer_unet=` / `scorer_encoder=`, e.g. from pointgroup_config); a call without one is refused as before.  The
-sparse scorers are assembled from this library's SparseConv3d family, as the backbone is.  Not served: the MinkowskiEngine
-backends and the panoptic tracker.
+sparse scorers are assembled from this library's SparseConv3d family, as the backbone is.  The panoptic tracker is served
+by panoptic_metrics.PanopticEvaluator (suppression, instance matching and AP on the device; INTEGRATION.md 1h);
+PanopticResults.get_instances below stays the host path it was.  Not served: the MinkowskiEngine backends.
 """
 from typing import Any, NamedTuple
 

@@ -1430,3 +1430,172 @@ def vote_add(votes, counts, workspace, errors, epoch, ids, out):
         with _lib.on_device(dev):
             _lib.call("tp3d_vote_add_f32", _lib.ptr(out), ld, _lib.ptr(ids), n, C, T, int(epoch), _lib.ptr(votes),
                       _lib.ptr(counts), _lib.ptr(workspace), _lib.ptr(errors), _lib.stream_ptr(dev))
+
+
+# ------------------------------------------------------------------------------------------- panoptic metrics (csrc/panoptic_metrics.hip)
+CLUSTER_BEST_WINDOW = 1024   # TP3D_CLUSTER_BEST_WINDOW: columns of one LDS histogram of tp3d_cluster_best_instance
+CLUSTER_MAX_PAIRS = (1 << 31) - 1  # ordered overlapping pairs (and slots, and clusters) the overlap kernels index
+
+
+def _cluster_vector(t, name, n):
+    if t.dim() != 1 or t.numel() != n:
+        raise ValueError("%s must be a vector of %d entries, got %s" % (name, n, tuple(t.shape)))
+    return _i64(t)
+
+
+def cluster_best_instance(clusters, column, gt_size, gt_class, cluster_class, col_lo, col_hi):
+    """The best ground-truth instance of every cluster of the ClusterSet `clusters`, from one integer histogram per
+    cluster: (inter_all, col_all, inter_cls, col_cls), each (K,) int64.
+
+    column (N,): the global ground-truth column of every point or -1, in the column layout of
+    torch_points_kernels.instance_iou; gt_size, gt_class (G,): the points and the class of every column; cluster_class
+    (K,): the class the cluster predicts; col_lo, col_hi (K,): the columns [col_lo, col_hi) of the cluster's cloud (a
+    member whose column lies outside is not counted).  With n the slots of the cluster and inter its members in a column:
+      col_all   the first maximum, over the columns with a member, of the fp32 IoU exactly as pointgroup.instance_iou_csr
+                forms it (fp32(inter) / max((fp32(n) + fp32(gt_size)) - fp32(inter), 1)): the `indices` of
+                instance_iou_csr(...).max(1) on every row whose maximum is positive; -1 on the others;
+      col_cls   the first maximum of the float64 IoU inter / (n + gt_size - inter) over the columns with a member and
+                gt_class == cluster_class: _Instance.find_best_match over the ground truth of the prediction's class
+                (metrics/panoptic_tracker.py:27-35); -1 without a candidate, and -1 as well when every candidate's
+                intersection is 0 (the reference then names the first candidate at IoU 0: a false positive at any
+                positive threshold);
+      inter_*   the members in that column (0 with -1): both IoUs are recomputed from the integers.
+    The histogram holds CLUSTER_BEST_WINDOW columns; a cloud with more instances is served window after window.  A
+    cluster that lists a point twice counts it twice, as instance_iou_csr does (the reference's np.intersect1d would count
+    it once; region growing produces no such cluster).  Nothing is read back and no (K, G) tensor is formed.  Device
+    tensors only."""
+    dev = _dev(clusters.members, clusters.starts, column, gt_size, gt_class, cluster_class, col_lo, col_hi)
+    K = len(clusters)
+    members, starts = _i64(clusters.members), _i64(clusters.starts)
+    if column.dim() != 1 or gt_size.dim() != 1 or tuple(gt_class.shape) != tuple(gt_size.shape):
+        raise ValueError("column must be (N,), gt_size and gt_class (G,)")
+    column, gt_size, gt_class = _i64(column), _i64(gt_size), _i64(gt_class)
+    cluster_class = _cluster_vector(cluster_class, "cluster_class", K)
+    col_lo, col_hi = _cluster_vector(col_lo, "col_lo", K), _cluster_vector(col_hi, "col_hi", K)
+    if K > CLUSTER_MAX_PAIRS:
+        raise ValueError("cluster_best_instance serves at most %d clusters" % CLUSTER_MAX_PAIRS)
+    out = [torch.empty((K,), dtype=torch.int64, device=dev) for _ in range(4)]
+    if K:
+        with _lib.on_device(dev):
+            _lib.call("tp3d_cluster_best_instance", _lib.ptr(members), _lib.ptr(starts), members.numel(), K, _lib.ptr(column),
+                      column.numel(), _lib.ptr(gt_size), _lib.ptr(gt_class), gt_size.numel(), _lib.ptr(cluster_class),
+                      _lib.ptr(col_lo), _lib.ptr(col_hi), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(out[3]),
+                      _lib.stream_ptr(dev))
+    return tuple(out)
+
+
+def cluster_overlaps(clusters, capacity=None, num_points=None, return_stats=False):
+    """The clusters every cluster shares a point with, as a CSR: (ov_start (K + 1,), ov_other (P,), ov_inter (P,)) int64.
+    Entries ov_start[k] : ov_start[k + 1] list the OTHER clusters that hold a point of cluster k, ascending, with the
+    number of shared points; both directions are stored.  This is pointgroup.cross_iou's intersection matrix without its
+    diagonal and without its zeros -- memory follows the slots and the overlapping pairs, never K * K.
+
+    The (point, cluster) slots are sorted by point (sorted-key core), every run of one point in m clusters contributes
+    its m * (m - 1) ordered pairs (counted per slot, placed by one block scan, written as 64-bit keys cluster * K +
+    other), the keys are sorted and their runs counted.  A point that one cluster lists twice is counted ONCE (the slots
+    are deduplicated per point, as the reference's 0/1 mask does; structures.py:33-35).
+
+    capacity=None: the arrays are exact; the call reads two integers back (the number of pairs before they are written,
+    the number of entries after).  capacity=c: nothing is read back; ov_other and ov_inter have c entries of which the
+    first ov_start[K] are meaningful, and when the pairs do not fit, ov_start is all zero and stats[2] = 1.
+    return_stats adds `stats` (3,) int64 on the device: ordered pairs, entries, overflow flag.  More than 2^31 - 1 pairs
+    (or slots, or clusters) are refused with ValueError.  num_points: an upper bound of the point indices (fewer sort
+    passes); members must lie in [0, 2^31).  Device tensors only."""
+    dev = _dev(clusters.members, clusters.starts, clusters.member_cluster)
+    K = len(clusters)
+    members, owner = _i64(clusters.members), _i64(clusters.member_cluster)
+    M = members.numel()
+    if owner.numel() != M:
+        raise ValueError("member_cluster must name the cluster of every slot")
+    if M > CLUSTER_MAX_PAIRS or K > CLUSTER_MAX_PAIRS or (capacity is not None and int(capacity) > CLUSTER_MAX_PAIRS):
+        raise ValueError("cluster_overlaps indexes at most 2^31 - 1 slots, clusters and pairs")
+    if capacity is not None and int(capacity) < 0:
+        raise ValueError("capacity must not be negative")
+    bits = 31 if num_points is None else max(1, int(max(int(num_points), 1) - 1).bit_length())
+    if bits > 31:
+        raise ValueError("cluster_overlaps serves point indices below 2^31")
+    stats = torch.empty((3,), dtype=torch.int64, device=dev)
+    h = _lib.load()
+    cbytes = h.tp3d_cluster_overlap_count_workspace_bytes(M) if M else 0
+    cws = _lib.workspace("cluster_overlap_count", cbytes, dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_cluster_overlap_count", _lib.ptr(members), _lib.ptr(owner), M, K, bits, _lib.ptr(stats), _lib.ptr(cws),
+                  cbytes, _lib.stream_ptr(dev))
+    if capacity is None:
+        cap = int(stats[0])  # device-to-host read 1 of 2
+        if cap > CLUSTER_MAX_PAIRS:
+            raise ValueError("cluster_overlaps: %d overlapping pairs are more than 2^31 - 1" % cap)
+    else:
+        cap = int(capacity)
+    ov_start = torch.empty((K + 1,), dtype=torch.int64, device=dev)
+    ov_other = torch.empty((cap,), dtype=torch.int64, device=dev)
+    ov_inter = torch.empty((cap,), dtype=torch.int64, device=dev)
+    ebytes = h.tp3d_cluster_overlap_emit_workspace_bytes(cap) if cap else 0
+    ews = _lib.workspace("cluster_overlap_emit", ebytes, dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_cluster_overlap_emit", _lib.ptr(owner), M, K, cap, _lib.ptr(ov_start), _lib.ptr(ov_other),
+                  _lib.ptr(ov_inter), _lib.ptr(stats), _lib.ptr(cws), cbytes, _lib.ptr(ews), ebytes, _lib.stream_ptr(dev))
+    if capacity is None:
+        P = int(stats[1])  # device-to-host read 2 of 2
+        ov_other, ov_inter = ov_other[:P], ov_inter[:P]
+    return (ov_start, ov_other, ov_inter, stats) if return_stats else (ov_start, ov_other, ov_inter)
+
+
+def cluster_nms(clusters, scores, threshold, overlaps=None, capacity=None):
+    """The greedy suppression of structures.non_max_suppression over the sparse overlaps: (keep (K,) bool, order (K,)
+    int64).  `order` is the visiting order: descending score, among equal scores the HIGHER index first (a stable
+    ascending sort read from the back, the rule box_nms documents).  The reference's numpy argsort is not stable, so the
+    order of equal scores is this project's definition, not the reference's.  A cluster that is still alive when visited
+    is kept and clears every neighbour whose IoU fp32(inter) / ((fp32(n_i) + fp32(n_j)) - fp32(inter)) is > the threshold
+    rounded to fp32 -- the arithmetic of pointgroup.cross_iou and of numpy's float32 comparison.  order[keep[order]] is
+    the list non_max_suppression(cross_iou(clusters), scores, threshold) returns.  A cluster without a neighbour it could
+    suppress is kept by a parallel pass; one workgroup walks the others in order.
+
+    overlaps: the result of cluster_overlaps (computed here when None, with `capacity` passed on: None costs its two
+    reads, a number none).  Nothing else is read back.  Device tensors only."""
+    dev = _dev(clusters.members, clusters.starts, scores)
+    K = len(clusters)
+    if scores.dim() != 1 or scores.numel() != K:
+        raise ValueError("one score per cluster is needed")
+    if K == 0:
+        return torch.zeros((0,), dtype=torch.bool, device=dev), torch.zeros((0,), dtype=torch.int64, device=dev)
+    if overlaps is None:
+        overlaps = cluster_overlaps(clusters, capacity=capacity)
+    ov_start, ov_other, ov_inter = (_i64(t) for t in overlaps[:3])
+    if ov_start.numel() != K + 1 or ov_other.numel() != ov_inter.numel():
+        raise ValueError("overlaps must be (ov_start (K + 1,), ov_other (P,), ov_inter (P,))")
+    order = torch.sort(scores.detach(), stable=True).indices.flip(0).contiguous()
+    starts = _i64(clusters.starts)
+    keep = torch.empty((K,), dtype=torch.uint8, device=dev)
+    hot = torch.empty((K,), dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_cluster_nms", _lib.ptr(order), _lib.ptr(starts), K, _lib.ptr(ov_start), _lib.ptr(ov_other),
+                  _lib.ptr(ov_inter), ov_other.numel(), float(threshold), _lib.ptr(hot), _lib.ptr(keep), _lib.stream_ptr(dev))
+    return keep.bool(), order
+
+
+def instance_ap_match(order, cls, cloud, valid, size, inter_cls, col_cls, gt_size, threshold):
+    """The true-positive flags of InstanceAPMeter._eval_cls (metrics/panoptic_tracker.py:57-79) for every (cloud, class)
+    group of one batch: tp (K,) bool.  order (K,): the clusters in visiting order (best first).  Cluster d is a true
+    positive when valid[d], its class-restricted best instance col_cls[d] exists, the float64 IoU inter_cls / (size +
+    gt_size[col_cls] - inter_cls) is >= threshold (not strict) and no earlier cluster of its cloud and class took that
+    instance.  The sibling of ap_match (detection), which compares strictly.  Nothing is read back.  Device tensors only."""
+    dev = _dev(order, cls, cloud, valid, size, inter_cls, col_cls, gt_size)
+    K = order.numel()
+    cls, cloud = _cluster_vector(cls, "cls", K), _cluster_vector(cloud, "cloud", K)
+    size, inter_cls, col_cls = (_cluster_vector(t, n, K) for t, n in ((size, "size"), (inter_cls, "inter_cls"),
+                                                                       (col_cls, "col_cls")))
+    gt_size = _i64(gt_size)
+    G = gt_size.numel()
+    tp = torch.zeros((K,), dtype=torch.uint8, device=dev)
+    if K:
+        valid8 = valid.to(torch.uint8).contiguous()
+        grouped = _i64(order)
+        grouped = grouped[torch.sort(cls[grouped], stable=True).indices]
+        grouped = grouped[torch.sort(cloud[grouped], stable=True).indices].contiguous()
+        taken = torch.empty((max(G, 1),), dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            _lib.call("tp3d_instance_ap_match", _lib.ptr(grouped), _lib.ptr(cls), _lib.ptr(cloud), _lib.ptr(valid8), K,
+                      _lib.ptr(size), _lib.ptr(inter_cls), _lib.ptr(col_cls), _lib.ptr(gt_size), G, float(threshold),
+                      _lib.ptr(taken), _lib.ptr(tp), _lib.stream_ptr(dev))
+    return tp.bool()
