@@ -5,180 +5,19 @@ There is no CPU fallback: if the library is missing or a call fails, the error i
 import collections
 import ctypes
 import os
+import types
 
 import torch  # noqa: F401  (loads the HIP runtime the library resolves against)
 
-from . import build as _build
+from . import build as _build, cabi
 
-_p = ctypes.c_void_p
-_i = ctypes.c_int
-_l = ctypes.c_int64
-_f = ctypes.c_float
-
-# name -> argtypes; every function returns int (0 = ok). Mirrors include/tp3d_hip.h one to one.
-SIGNATURES = {
-    "tp3d_fps_f32": [_p, _i, _i, _i, _p, _p, _p],
-    "tp3d_ball_query_dense_f32": [_p, _p, _i, _i, _i, _f, _i, _i, _p, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_ball_query_partial_dense_f32": [_p, _p, _p, _p, _l, _l, _f, _i, _i, _p, _p, _p, _i, _i, _p, ctypes.c_size_t,
-                                          _i, _p],
-    "tp3d_three_nn_f32": [_p, _p, _i, _i, _i, _p, _p, _p],
-    "tp3d_three_interpolate_fwd_f32": [_p, _p, _p, _i, _i, _i, _i, _p, _p],
-    "tp3d_three_interpolate_bwd_f32": [_p, _p, _p, _i, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_group_fwd_f32": [_p, _p, _i, _i, _i, _i, _i, _p, _p],
-    "tp3d_group_bwd_f32": [_p, _p, _i, _i, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_group_concat_fwd_f32": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p, _p],
-    "tp3d_rows_scatter_bwd_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_rows_scatter_invert": [_p, _p, _i, _i, _i, _i, _p, ctypes.c_size_t, _p],
-    "tp3d_rows_scatter_apply_f32": [_p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_bn_stats_f32": [_p, _l, _i, _f, _f, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p],
-    "tp3d_bn_act_f32": [_p, _p, _p, _p, _f, _l, _i, _p, _p],
-    "tp3d_bn_act_maxpool_f32": [_p, _p, _p, _p, _f, _l, _i, _i, _p, _p, _p],
-    "tp3d_bn_act_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _f, _l, _i, _i, _i, _p, _p, _p, _p, _p],
-    "tp3d_interp_concat_fwd_f32": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p],
-    "tp3d_idw_weights_f32": [_p, _l, _p, _p],
-    "tp3d_gemm_tn_f32": [_p, _p, _l, _i, _i, _p, _p, _p],
-    "tp3d_gemm_tn_x3_f32": [_p, _p, _l, _i, _i, _i, _p, _p, _i, _p],
-    "tp3d_gemm_tn_x3_act_f32": [_p, _p, _p, _p, _p, _f, _l, _i, _i, _i, _p, _p, _i, _p],
-    "tp3d_gemm_tn_x3_act_red_f32": [_p, _p, _p, _p, _p, _p, _f, _p, _i, _l, _i, _i, _i, _p, _p, _p, _p, _i, _p],
-    "tp3d_gemm_rows_narrow_f32": [_p, _p, _l, _i, _i, _p, _p, _i, _p],
-    "tp3d_gemm_tn_bn_narrow_f32": [_p, _p, _p, _p, _p, _p, _p, _f, _p, _l, _i, _i, _p, _p, _i, _p],
-    "tp3d_bn_bwd_reduce_f32": [_p, _p, _p, _p, _p, _p, _p, _f, _l, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p],
-    "tp3d_gemm_rows_f32": [_p, _p, _l, _i, _i, _p, _p, _p, _p],
-    "tp3d_gemm_rows_epi_f32": [_p, _p, _l, _i, _i, _p, _p, _p, _f, _p, _p, _p],
-    "tp3d_gemm_rows_bnact_sp_f32": [_p, _p, _p, _p, _f, _p, _l, _i, _i, _p, _p, _p, _i, _p],
-    "tp3d_gemm_rows_bnact_x3_f32": [_p, _p, _p, _p, _f, _p, _l, _i, _i, _p, _p, _p, _i, _p],
-    "tp3d_gemm_rows_bnbwd_sp_f32": [_p, _p, _p, _p, _p, _p, _p, _f, _p, _l, _i, _i, _p, _i, _i, _i, _p, _p, _i, _i, _p],
-    "tp3d_bn_finalize_f32": [_p, _i, _l, _i, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
-    "tp3d_kpconv_bwd_features_f32": [_p, _p, _p, _p, _p, _l, _l, _i, _i, _i, _f, _i, _i, _p, _p, ctypes.c_size_t, _i, _p,
-                                     ctypes.c_size_t, _p],
-    "tp3d_knn_partial_dense_f32": [_p, _p, _p, _p, _i, _i, _l, _l, _i, _f, _p, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_knn_dense_f32": [_p, _p, _i, _i, _i, _i, _f, _p, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_knn_interpolate_fwd_f32": [_p, _p, _p, _p, _l, _i, _i, _i, _i, _p, _p, _p],
-    "tp3d_nbr_maxpool_fwd_f32": [_p, _p, _l, _l, _i, _i, _p, _p, _p],
-    "tp3d_nbr_maxpool_bwd_f32": [_p, _p, _p, _l, _l, _i, _i, _p, _p, ctypes.c_size_t, _i, _p],
-    "tp3d_pospool_padding_i64": [_p, _l, _l, _p, _p],
-    "tp3d_pospool_fwd_f32": [_p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _f, _i, _i, _p, _p, _p],
-    "tp3d_pospool_bwd_f32": [_p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _f, _i, _i, _p, _p, ctypes.c_size_t, _i, _p],
-    "tp3d_voxel_bounds_f32": [_p, _p, _l, _f, _p, _p],
-    "tp3d_voxel_cluster_f32": [_p, _p, _l, _f, _p, _p, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_cluster_mean_f32": [_p, _p, _p, _l, _i, _p, _p],
-    "tp3d_cluster_majority_i64": [_p, _p, _p, _l, _l, _l, _p, _p],
-    "tp3d_kpconv_weighted_f32": [_p, _p, _p, _p, _p, _l, _l, _i, _i, _i, _f, _i, _i, _p, _p],
-    "tp3d_kpconv_deform_weighted_f32": [_p, _p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _i, _f, _i, _p, _p, _p, _p],
-    "tp3d_kpconv_deform_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _i, _f, _i, _p, _p, _p, _p,
-                                   ctypes.c_size_t, _i, _p, ctypes.c_size_t, _p],
-    "tp3d_gemm_skinny_f32": [_p, _p, _l, _i, _i, _i, _p, _p],
-    "tp3d_gemm_skinny_bnact_f32": [_p, _p, _l, _i, _i, _i, _p, _p, _p, _f, _p, _p],
-    "tp3d_randla_relpos_f32": [_p, _p, _p, _l, _i, _l, _p, _p],
-    "tp3d_attn_pool_fwd_f32": [_p, _p, _p, _l, _i, _i, _i, _i, _p, _p],
-    "tp3d_attn_pool_bwd_f32": [_p, _p, _p, _p, _l, _i, _i, _i, _i, _p, _p, _p],
-    "tp3d_randla_lfa_eval_f32": [_p, _p, _p, _p, _l, _l, _i, _i, _i, _i, _i, _p, _p, _p],
-    "tp3d_relation_rows_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p],
-    "tp3d_fps_ragged_f32": [_p, _p, _p, _l, _i, _i, _p, _p, _p],
-    "tp3d_table_edge_start_i64": [_p, _l, _i, _p, _p],
-    "tp3d_table_edge_col_i64": [_p, _p, _l, _i, _l, _p, _p],
-    "tp3d_pointconv_rows_f32": [_p, _p, _p, _p, _p, _l, _l, _l, _i, _i, _p, _p],
-    "tp3d_segment_max_fwd_f32": [_p, _p, _l, _l, _i, _i, _p, _p, _p],
-    "tp3d_segment_max_bwd_f32": [_p, _p, _p, _l, _l, _i, _i, _p, _p],
-    "tp3d_rsconv_relation_rows_f32": [_p, _p, _p, _p, _l, _l, _l, _i, _p, _p],
-    "tp3d_rsconv_msgmax_fwd_f32": [_p, _i, _p, _i, _p, _p, _l, _l, _l, _i, _p, _p, _p],
-    "tp3d_rsconv_msgmax_bwd_f32": [_p, _p, _p, _i, _p, _i, _p, _p, _l, _l, _l, _i, _p, _p, _p],
-    "tp3d_sparse_set_build_i32": [_p, _l, _i, _i, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_sparse_set_build_clouds_i32": [_p, _l, _i, _i, _i, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_sparse_kmap_i32": [_p, _l, _i, _i, _i, _p, _p, _p, _l, _p, _p],
-    "tp3d_sparse_kmap_mirror_i32": [_p, _l, _i, _p, _p],
-    "tp3d_sparse_conv_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _i, _p, _p],
-    "tp3d_sparse_wgrad_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_sparse_conv_wide_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _p, _p],
-    "tp3d_sparse_wgrad_wide_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_scale_fuse_fwd_f32": [_p, _i, _l, _i, _i, _f, _p, _p, _p, _p, _p],
-    "tp3d_scale_fuse_bwd_f32": [_p, _i, _l, _i, _i, _f, _p, _p, _p, _p, _p, _p],
-    "tp3d_pv_quantize_f32": [_p, _l, _i, _p, _p],
-    "tp3d_pv_trilinear_f32": [_p, _p, _l, _l, _i, _i, _p, _p],
-    "tp3d_pv_invert_i32": [_p, _l, _i, _l, _p, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_pv_gather_f32": [_p, _p, _p, _p, _l, _i, _l, _i, _p, _p],
-    "tp3d_pv_runsum_f32": [_p, _p, _p, _p, _p, _l, _i, _l, _i, _p, _p],
-    "tp3d_cluster_voxel_mean_fwd_f32": [_p, _i, _p, _p, _p, _l, _l, _l, _i, _p, _p],
-    "tp3d_cluster_voxel_mean_bwd_f32": [_p, _p, _p, _p, _p, _l, _l, _l, _i, _p, _p],
-    "tp3d_region_grow_f32": [_p, _p, _p, _l, _p, _i, _f, _l, _p, _p, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_feature_nn_f32": [_p, _p, _p, _p, _l, _l, _i, _f, _p, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_fgr_accumulate_f32": [_p, _p, _l, _i, _p, ctypes.c_size_t, _p],
-    "tp3d_fgr_solve": [_l, _i, ctypes.c_double, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_segment_transform_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _i, _i, _p, _p],
-    "tp3d_segment_transform_wgrad_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_segment_bcast_cat_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _i, _i, _p, _p],
-    "tp3d_segment_sum_f32": [_p, _p, _p, _l, _l, _i, _i, _i, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_box_nms_f32": [_p, _p, _p, _i, _i, _f, _p, _p],
-    "tp3d_box3d_iou_f64": [_p, _p, _l, _l, _p, _p],
-    "tp3d_box_best_gt_f64": [_p, _p, _p, _l, _p, _p, _p, _l, _l, _p, _p, _p],
-    "tp3d_ap_match": [_p, _p, _p, _l, _p, _p, _l, _p, _i, _p, _p, _p],
-    "tp3d_confusion_count_f32": [_p, _l, _i, _p, _p, _p, _l, _i, _i, _i, _l, _p, _p],
-    "tp3d_part_iou_counts_f32": [_p, _i, _p, _p, _l, _l, _i, _p, _p, _i, _p, _p, _p],
-    "tp3d_vote_add_f32": [_p, _i, _p, _l, _i, _l, _l, _p, _p, _p, _p, _p],
-    "tp3d_cluster_best_instance": [_p, _p, _l, _l, _p, _l, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p],
-    "tp3d_cluster_overlap_count": [_p, _p, _l, _l, _i, _p, _p, ctypes.c_size_t, _p],
-    "tp3d_cluster_overlap_emit": [_p, _l, _l, _l, _p, _p, _p, _p, _p, ctypes.c_size_t, _p, ctypes.c_size_t, _p],
-    "tp3d_cluster_nms": [_p, _p, _l, _p, _p, _p, _l, _f, _p, _p, _p],
-    "tp3d_instance_ap_match": [_p, _p, _p, _p, _l, _p, _p, _p, _p, _l, ctypes.c_double, _p, _p, _p],
-    # launch plans (host arithmetic; the last argument is a HOST int64 array)
-    "tp3d_gemm_tn_plan": [_l, _i, _i, _p],
-    "tp3d_gemm_tn_x3_plan": [_l, _i, _i, _p],
-    "tp3d_gemm_rows_plan": [_l, _i, _i, _p],
-    "tp3d_gemm_rows_small_plan": [_l, _i, _i, _p],
-    "tp3d_set_few_row_tiles": [_i],
-    "tp3d_bn_plan": [_l, _i, _i, _p],
-    "tp3d_scatter_plan": [_i, _i, _i, _i, _p],
-}
-_z = ctypes.c_size_t
-# name -> (restype, argtypes): version / error reporting and the host-side size and shape queries
-MISC = {
-    "tp3d_abi_version": (_i, []),
-    "tp3d_strerror": (ctypes.c_char_p, [_i]),
-    "tp3d_last_hip_error": (_i, []),
-    "tp3d_scatter_workspace_bytes": (_z, [_i, _i, _i, _i]),
-    "tp3d_bn_workspace_floats": (_z, [_l, _i]),
-    "tp3d_gemm_tn_workspace_floats": (_z, [_l, _i, _i]),
-    "tp3d_gemm_tn_x3_workspace_floats": (_z, [_l, _i, _i]),
-    "tp3d_gemm_tn_x3_serves": (_i, [_l, _i, _i]),
-    "tp3d_gemm_tn_x3_red_chunks": (_i, [_l, _i, _i]),
-    "tp3d_kpconv_bwd_workspace_bytes": (_z, [_l, _l]),
-    "tp3d_gemm_rows_stat_floats": (_z, [_l, _i]),
-    "tp3d_gemm_rows_stat_chunks": (_i, [_l, _i]),
-    "tp3d_gemm_rows_narrow_chunks": (_i, [_l]),
-    "tp3d_gemm_tn_bn_narrow_serves": (_i, [_l, _i, _i]),
-    "tp3d_gemm_tn_bn_narrow_workspace_floats": (_z, [_l, _i, _i]),
-    "tp3d_gemm_rows_bnbwd_sp_serves": (_i, [_l, _i, _i]),
-    "tp3d_gemm_rows_x3_chunks": (_i, [_l, _i, _i, _i]),
-    "tp3d_gemm_rows_sp_chunks": (_i, [_l, _i, _i, _i]),
-    "tp3d_gemm_rows_workspace_floats": (_z, [_l, _i, _i]),
-    "tp3d_kpconv_grad_workspace_bytes": (_z, [_l, _l, _i]),
-    "tp3d_knn_workspace_bytes": (_z, [_i, _l, _i]),
-    "tp3d_voxel_workspace_bytes": (_z, [_l]),
-    "tp3d_ball_query_workspace_bytes": (_z, [_i, _l, _i]),
-    "tp3d_sparse_workspace_bytes": (_z, [_l]),
-    "tp3d_sparse_cloud_limit_max": (_i, []),
-    "tp3d_sparse_wgrad_chunks": (_i, [_l, _i, _i, _i]),
-    "tp3d_sparse_wgrad_workspace_floats": (_z, [_l, _i, _i, _i]),
-    "tp3d_sparse_conv_wide_serves": (_i, [_i, _i, _i]),
-    "tp3d_sparse_wgrad_wide_chunks": (_i, [_l, _i, _i, _i]),
-    "tp3d_sparse_wgrad_wide_workspace_floats": (_z, [_l, _i, _i, _i]),
-    "tp3d_pv_invert_workspace_bytes": (_z, [_l, _i]),
-    "tp3d_region_grow_workspace_bytes": (_z, [_l]),
-    "tp3d_feature_nn_workspace_bytes": (_z, [_l, _l, _i]),
-    "tp3d_fgr_workspace_bytes": (_z, [_l]),
-    "tp3d_segment_tile_rows": (_i, []),
-    "tp3d_segment_sum_chunk": (_i, []),
-    "tp3d_segment_transform_wgrad_workspace_bytes": (_z, [_l, _l, _i]),
-    "tp3d_segment_sum_workspace_bytes": (_z, [_l, _l, _i]),
-    "tp3d_box_nms_max_boxes": (_i, []),
-    "tp3d_confusion_tile_rows": (_i, []),
-    "tp3d_confusion_lds_max_classes": (_i, []),
-    "tp3d_part_iou_max_parts": (_i, []),
-    "tp3d_cluster_best_window": (_i, []),
-    "tp3d_cluster_overlap_count_workspace_bytes": (_z, [_l]),
-    "tp3d_cluster_overlap_emit_workspace_bytes": (_z, [_l]),
-}
-ABI_VERSION = 39
+# name -> (restype, argtypes) of every entry point, and the header's integer #defines: include/tp3d_hip.h is the only
+# statement of the ABI (the compiler holds every definition to it, cabi reads the ctypes from it)
+FUNCTIONS, CONSTANTS = cabi.parse_header(os.path.join(_build.ROOT, "include", "tp3d_hip.h"))
+# read-only views of FUNCTIONS under the names of the former hand-written tables
+SIGNATURES = types.MappingProxyType({name: argtypes for name, (_, argtypes) in FUNCTIONS.items()})
+MISC = types.MappingProxyType(FUNCTIONS)
+ABI_VERSION = CONSTANTS["TP3D_ABI_VERSION"]  # load() refuses a library built from another header
 
 _handle = None
 
@@ -202,12 +41,8 @@ def load():
     if not os.path.exists(path):
         raise Tp3dError("libtp3d_hip.so is missing at %s and could not be built" % path)
     h = ctypes.CDLL(path)
-    for name, argtypes in SIGNATURES.items():
+    for name, (restype, argtypes) in FUNCTIONS.items():
         fn = getattr(h, name)  # AttributeError here = the .so does not match the header
-        fn.argtypes = argtypes
-        fn.restype = _i
-    for name, (restype, argtypes) in MISC.items():
-        fn = getattr(h, name)
         fn.restype = restype
         fn.argtypes = argtypes
     if h.tp3d_abi_version() != ABI_VERSION:

@@ -48,6 +48,9 @@ def _i64(t):
     return t.contiguous()
 
 
+FPS_MAX_REG_POINTS = _lib.CONSTANTS["TP3D_FPS_MAX_REG_POINTS"]  # larger clouds keep the running min-distance in HBM
+
+
 def furthest_point_sample(xyz, npoint):
     """xyz (B,N,3) float -> (B,npoint) int64 indices; starts at point 0, ties -> lowest index."""
     if xyz.dim() != 3 or xyz.shape[2] != 3:
@@ -59,7 +62,7 @@ def furthest_point_sample(xyz, npoint):
     B, N, _ = xyz.shape
     out = torch.empty((B, npoint), dtype=torch.int64, device=dev)
     scratch = None
-    if N > 32768:  # TP3D_FPS_MAX_REG_POINTS: larger clouds keep the running min-distance in HBM
+    if N > FPS_MAX_REG_POINTS:
         scratch = torch.empty((B, N), dtype=torch.float32, device=dev)
     with _lib.on_device(dev):
         _lib.call("tp3d_fps_f32", _lib.ptr(xyz), B, N, int(npoint), _lib.ptr(scratch), _lib.ptr(out),
@@ -111,7 +114,7 @@ def fps_ragged(pos, batch, ratio=None, counts=None):
     if total == 0:
         return out
     seg_out = seg_out_host.to(dev)
-    scratch = torch.empty(M, dtype=torch.float32, device=dev) if nmax > 32768 else None  # TP3D_FPS_MAX_REG_POINTS
+    scratch = torch.empty(M, dtype=torch.float32, device=dev) if nmax > FPS_MAX_REG_POINTS else None
     with _lib.on_device(dev):
         _lib.call("tp3d_fps_ragged_f32", _lib.ptr(pos), _lib.ptr(seg_in), _lib.ptr(seg_out), M, nclouds, nmax,
                   _lib.ptr(scratch), _lib.ptr(out), _lib.stream_ptr(dev))
@@ -1221,7 +1224,7 @@ def segment_mean_rows(rows, seg):
 
 
 # ------------------------------------------------------------------------------------------- detection (csrc/detection.hip)
-BOX_NMS_MAX_BOXES = 4096  # TP3D_BOX_NMS_MAX_BOXES
+BOX_NMS_MAX_BOXES = _lib.CONSTANTS["TP3D_BOX_NMS_MAX_BOXES"]
 
 
 def box_nms(boxes, scores, classes, overlap_threshold=0.25):
@@ -1372,7 +1375,7 @@ def confusion_count(cm, labels, scores=None, pred=None, ignore_label=None, row_i
     return cm
 
 
-PART_IOU_MAX_PARTS = 16  # TP3D_PART_IOU_MAX_PARTS of include/tp3d_hip.h
+PART_IOU_MAX_PARTS = _lib.CONSTANTS["TP3D_PART_IOU_MAX_PARTS"]
 
 
 def part_iou_counts(scores, labels, seg, part_lo, part_hi, max_parts):
@@ -1433,7 +1436,8 @@ def vote_add(votes, counts, workspace, errors, epoch, ids, out):
 
 
 # ------------------------------------------------------------------------------------------- panoptic metrics (csrc/panoptic_metrics.hip)
-CLUSTER_BEST_WINDOW = 1024   # TP3D_CLUSTER_BEST_WINDOW: columns of one LDS histogram of tp3d_cluster_best_instance
+# columns of one LDS histogram of tp3d_cluster_best_instance
+CLUSTER_BEST_WINDOW = _lib.CONSTANTS["TP3D_CLUSTER_BEST_WINDOW"]
 CLUSTER_MAX_PAIRS = (1 << 31) - 1  # ordered overlapping pairs (and slots, and clusters) the overlap kernels index
 
 

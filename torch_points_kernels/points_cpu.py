@@ -23,9 +23,8 @@ import os
 
 import torch
 
-from torch_points3d_amd import build as _build
+from torch_points3d_amd import build as _build, cabi
 
-_p, _l, _i, _f = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
 _h = None
 _threads = 1
 
@@ -37,15 +36,10 @@ def _lib():
         if not os.path.exists(path):
             _build.build_cpu_library()
         h = ctypes.CDLL(path)
-        h.tp3d_cpu_grid_build.restype = _p
-        h.tp3d_cpu_grid_build.argtypes = [_p, _l, _f]
-        h.tp3d_cpu_grid_free.restype = None
-        h.tp3d_cpu_grid_free.argtypes = [_p]
-        h.tp3d_cpu_ball_count.argtypes = [_p, _p, _l, _f, _p, _i]
-        h.tp3d_cpu_ball_fill.argtypes = [_p, _p, _l, _f, _i, _i, _p, _p, _p, _i]
-        h.tp3d_cpu_knn.argtypes = [_p, _p, _l, _i, _p, _p, _i]
-        h.tp3d_cpu_grow_clusters.restype = _l
-        h.tp3d_cpu_grow_clusters.argtypes = [_p, _l, _i, _l, _p, _p]
+        functions, _ = cabi.parse_header(os.path.join(_build.ROOT, "include", "tp3d_cpu.h"))
+        for name, (restype, argtypes) in functions.items():
+            fn = getattr(h, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if h.tp3d_cpu_abi_version() != 2:
             raise RuntimeError("libtp3d_cpu.so ABI mismatch")
         _h = h
