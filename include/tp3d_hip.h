@@ -760,6 +760,46 @@ int tp3d_fgr_accumulate_f32(const float *xyz, const float *xyz_target, int64_t N
                             size_t workspace_bytes, void *stream);
 int tp3d_fgr_solve(int64_t N, int iter, double mu_init, float *T, void *workspace, size_t workspace_bytes, void *stream);
 
+/* RANSAC over correspondences and the weighted Kabsch refit (csrc/ransac.hip, csrc/ransac_horn.h)
+ *                                                   [utils/registration.py:24-43, :141-163; open3d's correspondence RANSAC]
+ *   xyz, xyz_target (N, 3) fp32: correspondence i pairs xyz[i] with xyz_target[i]; 3 <= N < 2^31 / 3.
+ *   tp3d_ransac_score_f32: samples (H, n) int64, 3 <= n <= 8, entries in [0, N), repeats allowed -> poses (H, 12) fp32 (row-
+ *     major [R | t]; NULL: kept in the workspace) and counts (H) int32.  The pose of a hypothesis maps its n sampled
+ *     sources onto their targets in the least-squares sense, in double by Horn's closed form: centred cross-covariance,
+ *     the symmetric 4 x 4 matrix, the unit eigenvector of its largest eigenvalue by cyclic Jacobi sweeps, that quaternion
+ *     as R, t = mean(q) - R mean(p) -- Kabsch with the determinant correction, a proper rotation by construction.  One
+ *     thread per hypothesis, the pose computed once.  counts[h] = the number of i with |R p_i + t - q_i|^2 <
+ *     threshold^2 in fp32: s_a = fma(R_a0, px, fma(R_a1, py, fma(R_a2, pz, t_a))), d_a = s_a - q_a,
+ *     d2 = fma(dz, dz, fma(dy, dy, dx * dx)).  A pose that is not finite (or a sampled row outside [0, N), which is
+ *     never dereferenced) gives NaNs and the count 0.  N is split over workgroups in whole tiles of TP3D_RANSAC_TILE
+ *     (tp3d_ransac_splits(N, H) splits) and the per-split counts are added as integers in split order: repeats are
+ *     bit-equal, nothing of size H * N exists.
+ *   tp3d_ransac_select: the hypothesis of the highest count, among equal counts the LOWEST index (the integer maximum
+ *     of (count << 32) | (0xffffffff - h), H <= 2^31; open3d compares the inlier RMSE of equal counts instead).  Its
+ *     index, count and pose (formed again in double) go to the head of the workspace; the host reads nothing.
+ *   tp3d_kabsch_accumulate_f32 + tp3d_kabsch_solve with the same N, gate and workspace: the weighted Kabsch pose.  The
+ *     weight of correspondence i is weight[i] (NULL: 1), and with gate != 0 only correspondences with |R p + t - q|^2 <
+ *     threshold^2 in double under the pose of the workspace weigh in.  accumulate: per-block sums in double of w, w p,
+ *     w q, w p_a q_b, the gated count and the gated sum of squared distances.  solve (one wave): the partials added in
+ *     block order, centred, Horn as above; the pose goes to the workspace and, as 16 floats row-major, to T (may be
+ *     NULL).  If the weight sum is 0, or with the gate fewer than 3 correspondences are gated in, the previous pose
+ *     stays; without a previous pose (gate == 0 starts afresh) the result is the identity.  update == 0 leaves the pose
+ *     and only records the stats.
+ *   The head of the workspace, doubles: [0, 12) pose, 12 whether there is one, 13 best index, 14 best count, 15 gated
+ *     count and 16 gated sum of d^2 of the last accumulate, 17 its weight sum.  tp3d_ransac_workspace_bytes(N, H): H = 0
+ *     for the Kabsch entry points alone; 0 = not served. */
+#define TP3D_RANSAC_TILE 256
+#define TP3D_RANSAC_HYP_BLOCK 256
+size_t tp3d_ransac_workspace_bytes(int64_t N, int64_t H);
+int tp3d_ransac_splits(int64_t N, int64_t H);
+int tp3d_ransac_score_f32(const float *xyz, const float *xyz_target, int64_t N, const int64_t *samples, int64_t H, int n,
+                          float threshold, float *poses, int32_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+int tp3d_ransac_select(const float *xyz, const float *xyz_target, int64_t N, const int64_t *samples, int64_t H, int n,
+                       const int32_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+int tp3d_kabsch_accumulate_f32(const float *xyz, const float *xyz_target, const float *weight, int64_t N, int gate,
+                               double threshold, void *workspace, size_t workspace_bytes, void *stream);
+int tp3d_kabsch_solve(int64_t N, int gate, int update, float *T, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Per-cloud row kernels of PointNet (csrc/segment_rows.hip)
  *                                  [core/common_modules/spatial_transform.py:44-49, modules/PointNet/modules.py:33-35, :108]
  *   seg (B + 1) int64: the row offsets of the clouds, ascending, seg[0] = 0, seg[B] = N, empty clouds allowed; fp32 data;

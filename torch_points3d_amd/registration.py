@@ -9,14 +9,19 @@ device: fragment descriptors trained with a mined contrastive loss, evaluated by
   BatchHardContrastiveLoss         the per-pair Python loop as one feature_nn call with the spatial exclusion
   get_matches, estimate_transfo, fast_global_registration   utils/registration.py (1-NN by feature_nn, FGR by torchpoints.fgr)
   compute_hit_ratio, compute_transfo_error, compute_scaled_registration_error, compute_registration_recall
+  ransac_registration              utils/registration.py:141-163 through torchpoints.ransac_pose (HIP hypothesis scoring, integer
+                                   select, Kabsch refit over the inliers; nothing read back); CPU tensors: numpy float64
   evaluate_pair                    the tracker's sequence for one fragment pair (registration_tracker.py:123-145)
+  compute_metrics                  the benchmark script's figures for one pair (scripts/test_registration_scripts/evaluate.py:
+                                   46-142), with the RANSAC block the script left unimplemented
   FragmentDescriptor               backbone -> FC_layer head (FragmentKPConv's layout) -> unit rows; "match" mode loss
 
-MS-SVConv lives in ms_svconv.py.  Not served: RANSAC (open3d), TEASER++, the Minkowski and patch models, and
-compute_loss_label's pytorch_metric_learning miners.
+MS-SVConv lives in ms_svconv.py.  Not served: TEASER++, the Minkowski and patch models, and compute_loss_label's
+pytorch_metric_learning miners.
 """
 import math
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -175,6 +180,84 @@ def fast_global_registration(xyz, xyz_target, mu_init=1, num_iter=20):
     return tp.fgr(xyz, xyz_target, mu_init=float(mu_init), num_iter=num_iter)
 
 
+def _horn_numpy(p, q, w=None):
+    """(..., 3, 4) float64 [R | t]: the weighted least-squares rigid pose of p (..., n, 3) onto q by Horn's closed form, the
+    unit eigenvector of the largest eigenvalue of the symmetric 4 x 4 matrix of the centred cross-covariance (what
+    csrc/ransac_horn.h does with Jacobi sweeps, here numpy's eigh)"""
+    w = np.ones(p.shape[:-1]) if w is None else w
+    wsum = w.sum(-1)[..., None]
+    mp, mq = (w[..., None] * p).sum(-2) / wsum, (w[..., None] * q).sum(-2) / wsum
+    S = np.einsum("...n,...na,...nb->...ab", w, p - mp[..., None, :], q - mq[..., None, :])
+    A = np.empty(S.shape[:-2] + (4, 4))
+    A[..., 0, 0] = S[..., 0, 0] + S[..., 1, 1] + S[..., 2, 2]
+    A[..., 1, 1] = S[..., 0, 0] - S[..., 1, 1] - S[..., 2, 2]
+    A[..., 2, 2] = S[..., 1, 1] - S[..., 0, 0] - S[..., 2, 2]
+    A[..., 3, 3] = S[..., 2, 2] - S[..., 0, 0] - S[..., 1, 1]
+    A[..., 0, 1] = A[..., 1, 0] = S[..., 1, 2] - S[..., 2, 1]
+    A[..., 0, 2] = A[..., 2, 0] = S[..., 2, 0] - S[..., 0, 2]
+    A[..., 0, 3] = A[..., 3, 0] = S[..., 0, 1] - S[..., 1, 0]
+    A[..., 1, 2] = A[..., 2, 1] = S[..., 0, 1] + S[..., 1, 0]
+    A[..., 1, 3] = A[..., 3, 1] = S[..., 2, 0] + S[..., 0, 2]
+    A[..., 2, 3] = A[..., 3, 2] = S[..., 1, 2] + S[..., 2, 1]
+    qw, qx, qy, qz = np.moveaxis(np.linalg.eigh(A)[1][..., :, 3], -1, 0)  # (eigh: ascending eigenvalues, unit vectors)
+    R = np.stack([np.stack([qw * qw + qx * qx - qy * qy - qz * qz, 2 * (qx * qy - qw * qz), 2 * (qx * qz + qw * qy)], -1),
+                  np.stack([2 * (qx * qy + qw * qz), qw * qw - qx * qx + qy * qy - qz * qz, 2 * (qy * qz - qw * qx)], -1),
+                  np.stack([2 * (qx * qz - qw * qy), 2 * (qy * qz + qw * qx), qw * qw - qx * qx - qy * qy + qz * qz], -1)], -2)
+    t = mq - np.einsum("...ab,...b->...a", R, mp)
+    return np.concatenate([R, t[..., None]], -1)
+
+
+def _ransac_numpy(xyz, xyz_target, threshold, samples, refine=1):
+    """the algorithm of torchpoints.ransac_pose in numpy float64, for CPU tensors: (pose (3, 4), best index, counts (H,))"""
+    p, q = xyz.astype(np.float64), xyz_target.astype(np.float64)
+    H, N = len(samples), len(p)
+    poses = _horn_numpy(p[samples], q[samples])
+    counts = np.zeros(H, dtype=np.int64)
+    step = max(1, (1 << 21) // N)  # (the (step, N, 3) residuals stay within a few tens of MB)
+    for h0 in range(0, H, step):
+        P = poses[h0:h0 + step]
+        d = np.einsum("hab,nb->hna", P[:, :, :3], p) + P[:, None, :, 3] - q
+        hit = (d * d).sum(-1) < threshold * threshold
+        counts[h0:h0 + step] = np.where(np.isfinite(P).all((1, 2)), hit.sum(1), 0)
+    best = int(np.argmax(counts))  # the first of equal counts
+    pose = poses[best] if np.isfinite(poses[best]).all() else np.eye(4)[:3]
+    for _ in range(refine):
+        d = p @ pose[:, :3].T + pose[:, 3] - q
+        inl = (d * d).sum(1) < threshold * threshold
+        if inl.sum() >= 3:
+            fresh = _horn_numpy(p[inl], q[inl])
+            pose = fresh if np.isfinite(fresh).all() else pose
+    return pose, best, counts
+
+
+def ransac_registration(xyz, xyz_target, distance_threshold=0.05, num_iterations=80000, *, generator=None, samples=None):
+    """utils/registration.py:141-163 (open3d's registration_ransac_based_on_correspondence with ransac_n = 4 and point-to-
+    point estimation) for the correspondences xyz[i] <-> xyz_target[i]: `num_iterations` hypotheses from 4 correspondences
+    drawn with replacement (samples (H, 4) int64; default torch.randint on the inputs' device with `generator`), each
+    scored by its number of correspondences within distance_threshold, the best refitted once by Kabsch over its inliers.
+    Device tensors go through torchpoints.ransac_pose (HIP, nothing read back), CPU tensors through a numpy float64
+    restatement of the same algorithm.  Returns the (4, 4) float pose ON THE INPUTS' DEVICE (the reference returns a CPU
+    tensor).  Differences from open3d: every hypothesis is scored (no early exit on a confidence bound, no edge-length
+    or distance checkers), and among hypotheses with equal inlier counts the lowest index wins, an integer rule (open3d
+    compares their inlier RMSE)."""
+    assert xyz.shape == xyz_target.shape
+    if xyz.device.type != "cpu":
+        return tp.ransac_pose(xyz, xyz_target, float(distance_threshold), num_iterations=num_iterations, ransac_n=4, refine=1,
+                              samples=samples, generator=generator)[0]
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or len(xyz) < 3:
+        raise ValueError("ransac_registration: xyz and xyz_target must both be (N, 3) with N >= 3")
+    if samples is None:
+        if num_iterations < 1:
+            raise ValueError("ransac_registration: at least one hypothesis is needed")
+        samples = torch.randint(0, len(xyz), (int(num_iterations), 4), generator=generator)
+    if samples.dim() != 2 or not 3 <= samples.shape[1] <= tp.RANSAC_MAX_N or len(samples) < 1:
+        raise ValueError("ransac_registration: samples must be (H, n) with H >= 1 and 3 <= n <= %d" % tp.RANSAC_MAX_N)
+    pose = _ransac_numpy(xyz.detach().numpy(), xyz_target.detach().numpy(), float(distance_threshold), samples.long().numpy())[0]
+    T = torch.eye(4)
+    T[:3] = torch.from_numpy(pose).float()
+    return T
+
+
 # ------------------------------------------------------------------------------------------------------------------ metrics
 def compute_hit_ratio(xyz, xyz_target, T_gt, tau_1):
     """the share of correspondences closer than tau_1 under T_gt (registration_metrics.py:30-37)"""
@@ -231,6 +314,43 @@ def evaluate_pair(feat, feat_target, xyz, xyz_target, matches_gt, num_points=500
     sr_err = compute_scaled_registration_error(xyz, T_gt, T_pred)
     return {"hit_ratio": hit_ratio, "feat_match_ratio": (hit_ratio > tau_2).to(torch.float), "trans_error": trans_error,
             "rot_error": rot_error, "sr_err": sr_err}
+
+
+def _pose_figures(res, tag, xyz, T_gt, T_est, rot_thresh, trans_thresh, xyz_gt, xyz_target_gt, recall_thresh):
+    trans_error, rot_error = compute_transfo_error(T_est, T_gt)
+    res["trans_error_" + tag] = trans_error
+    res["rot_error_" + tag] = rot_error
+    res["rre_" + tag] = (rot_error < rot_thresh).to(torch.float)
+    res["rte_" + tag] = (trans_error < trans_thresh).to(torch.float)
+    res["sr_" + tag] = compute_scaled_registration_error(xyz, T_gt, T_est)
+    if xyz_gt is not None and xyz_target_gt is not None:
+        res["registration_recall_" + tag] = compute_registration_recall(xyz_gt, xyz_target_gt, T_est, recall_thresh)
+
+
+def compute_metrics(xyz, xyz_target, feat, feat_target, T_gt, sym=False, tau_1=0.1, tau_2=0.05, rot_thresh=5, trans_thresh=5,
+                    use_ransac=False, ransac_thresh=0.02, registration_recall_thresh=0.2, xyz_gt=None, xyz_target_gt=None, *,
+                    ransac_iterations=80000, generator=None, samples=None):
+    """The figures of scripts/test_registration_scripts/evaluate.py:46-142 for one fragment pair, as a dict of scalars on
+    the inputs' device (the script reads every one back with .item(); its time_* entries are not kept): 1-NN feature
+    matches (mutual ones with sym), hit_ratio under T_gt at tau_1, feat_match_ratio = hit_ratio > tau_2, and for the
+    FGR pose of the matched positions trans_error_fgr, rot_error_fgr, rre_fgr = rot_error < rot_thresh, rte_fgr =
+    trans_error < trans_thresh, sr_fgr, and registration_recall_fgr when xyz_gt and xyz_target_gt are given.
+    use_ransac=True adds the same entries with the suffix _ransac for ransac_registration(..., ransac_thresh), the block
+    the script ends in NotImplementedError (ransac_iterations, generator, samples: its hypotheses).  TEASER++ is not
+    served: there is no use_teaser."""
+    res = dict()
+    matches_pred = get_matches(feat, feat_target, sym=sym)
+    src, tgt = xyz[matches_pred[:, 0]], xyz_target[matches_pred[:, 1]]
+    hit_ratio = compute_hit_ratio(src, tgt, T_gt, tau_1)
+    res["hit_ratio"] = hit_ratio
+    res["feat_match_ratio"] = (hit_ratio > tau_2).to(torch.float)
+    T_fgr = fast_global_registration(src, tgt)
+    _pose_figures(res, "fgr", xyz, T_gt, T_fgr, rot_thresh, trans_thresh, xyz_gt, xyz_target_gt, registration_recall_thresh)
+    if use_ransac:
+        T_ransac = ransac_registration(src, tgt, ransac_thresh, ransac_iterations, generator=generator, samples=samples)
+        _pose_figures(res, "ransac", xyz, T_gt, T_ransac, rot_thresh, trans_thresh, xyz_gt, xyz_target_gt,
+                      registration_recall_thresh)
+    return res
 
 
 # -------------------------------------------------------------------------------------------------------------------- model

@@ -19,7 +19,7 @@ from . import _lib
 
 __all__ = ["furthest_point_sample", "ball_query", "three_nn", "three_interpolate", "grouping_operation"]
 # (message-passing side: fps_quota, fps_ragged, radius_edges, pointconv_rows, segment_max, rsconv_relation_rows,
-# rsconv_msgmax; PointGroup's clustering: ClusterSet, region_grow_csr; registration: feature_nn, gather_rows, fgr --
+# rsconv_msgmax; PointGroup's clustering: ClusterSet, region_grow_csr; registration: feature_nn, gather_rows, fgr, ransac_score, kabsch, ransac_pose --
 # further down)
 
 
@@ -1031,6 +1031,137 @@ def fgr(xyz, xyz_target, mu_init=1.0, num_iter=20):
             _lib.call("tp3d_fgr_accumulate_f32", _lib.ptr(xyz), _lib.ptr(xyz_target), N, i, _lib.ptr(ws), nbytes, stream)
             _lib.call("tp3d_fgr_solve", N, i, float(mu_init), _lib.ptr(T), _lib.ptr(ws), nbytes, stream)
     return T
+
+
+# ------------------------------------------------------------------------------------------------ RANSAC (csrc/ransac.hip)
+RANSAC_TILE = _lib.CONSTANTS["TP3D_RANSAC_TILE"]            # correspondences per tile: N is split over workgroups in tiles
+RANSAC_HYP_BLOCK = _lib.CONSTANTS["TP3D_RANSAC_HYP_BLOCK"]  # hypotheses per workgroup of the score kernel
+RANSAC_MAX_N = 8                                            # largest sample size (RS_MAX_N of csrc/ransac.hip)
+
+
+class NotOnDeviceError(RuntimeError, ValueError):
+    """_dev's refusal of a CPU tensor (a RuntimeError, as everywhere in this module) that is also the ValueError the
+    argument checks of the RANSAC operators raise"""
+
+
+def _dev_checked(*tensors):
+    try:
+        return _dev(*tensors)
+    except RuntimeError as e:
+        raise NotOnDeviceError(str(e)) from None
+
+
+def _correspondences(xyz, xyz_target, what):
+    dev = _dev_checked(xyz, xyz_target)
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape != xyz_target.shape:
+        raise ValueError("%s: xyz and xyz_target must both be (N, 3)" % what)
+    if xyz.shape[0] < 3:
+        raise ValueError("%s: at least 3 correspondences are needed, got %d" % (what, xyz.shape[0]))
+    return dev, _f32(xyz), _f32(xyz_target)
+
+
+def _ransac_samples(samples, N, num_iterations, ransac_n, dev, generator):
+    if samples is None:
+        if num_iterations < 1:
+            raise ValueError("ransac: at least one hypothesis is needed, got %d" % num_iterations)
+        if not 3 <= ransac_n <= RANSAC_MAX_N:
+            raise ValueError("ransac: ransac_n must lie in [3, %d], got %d" % (RANSAC_MAX_N, ransac_n))
+        return torch.randint(0, N, (int(num_iterations), int(ransac_n)), device=dev, generator=generator)
+    if _dev_checked(samples) != dev:
+        raise NotOnDeviceError("all tensors must be on the same device (%s vs %s)" % (dev, samples.device))
+    if samples.dim() != 2 or not 3 <= samples.shape[1] <= RANSAC_MAX_N:
+        raise ValueError("ransac: samples must be (H, n) with 3 <= n <= %d, got %s" % (RANSAC_MAX_N, tuple(samples.shape)))
+    if samples.shape[0] < 1:
+        raise ValueError("ransac: at least one hypothesis is needed, got %d" % samples.shape[0])
+    return _i64(samples)
+
+
+def _ransac_workspace(N, H, dev):
+    nbytes = _lib.load().tp3d_ransac_workspace_bytes(N, H)
+    if nbytes == 0:
+        raise ValueError("ransac: %d correspondences and %d hypotheses are not served" % (N, H))
+    return _lib.workspace("ransac", nbytes, dev), nbytes
+
+
+def ransac_score(xyz, xyz_target, samples, threshold):
+    """The hypotheses of a RANSAC over the correspondences xyz[i] <-> xyz_target[i], both (N, 3), N >= 3: for every row of
+    samples (H, n) int64 (3 <= n <= 8, entries in [0, N), repeats allowed as in open3d's draw with replacement) the rigid
+    pose that maps the n sampled sources onto their targets in the least-squares sense, and the number of correspondences
+    it explains: (poses (H, 3, 4) fp32 [R | t], counts (H,) int32) with counts[h] = #{i : |R p_i + t - q_i|^2 <
+    threshold^2} in fp32.  The pose is computed in double by Horn's closed form (Kabsch with the determinant correction,
+    utils/registration.py:24-43: a proper rotation by construction) and rounded once.  A hypothesis whose pose is not
+    finite gets NaNs and the count 0.  Integer sums only: repeats are bit-equal.  Device tensors only."""
+    dev, xyz, xyz_target = _correspondences(xyz, xyz_target, "ransac_score")
+    samples = _ransac_samples(samples, xyz.shape[0], 0, 0, dev, None)
+    N, (H, n) = xyz.shape[0], samples.shape
+    ws, nbytes = _ransac_workspace(N, H, dev)
+    poses = torch.empty((H, 3, 4), dtype=torch.float32, device=dev)
+    counts = torch.empty((H,), dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_ransac_score_f32", _lib.ptr(xyz), _lib.ptr(xyz_target), N, _lib.ptr(samples), H, n, float(threshold),
+                  _lib.ptr(poses), _lib.ptr(counts), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+    return poses, counts
+
+
+def kabsch(xyz, xyz_target, weight=None):
+    """The (4, 4) fp32 pose that maps xyz onto xyz_target, both (N, 3), N >= 3, in the (weighted) least-squares sense
+    (estimate_transfo, utils/registration.py:24-43, with optional weights (N,) >= 0): per-block sums in double, one wave
+    that centres them and runs Horn's closed form, so det R = +1 also for mirrored or planar input.  A weight sum of 0
+    gives the identity.  Repeats are bit-equal.  Device tensors only."""
+    dev, xyz, xyz_target = _correspondences(xyz, xyz_target, "kabsch")
+    N = xyz.shape[0]
+    if weight is not None:
+        _dev_checked(xyz, weight)
+        if tuple(weight.shape) != (N,):
+            raise ValueError("kabsch: weight must be (N,) = (%d,), got %s" % (N, tuple(weight.shape)))
+        weight = _f32(weight)
+    ws, nbytes = _ransac_workspace(N, 0, dev)
+    T = torch.empty((4, 4), dtype=torch.float32, device=dev)
+    stream = _lib.stream_ptr(dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_kabsch_accumulate_f32", _lib.ptr(xyz), _lib.ptr(xyz_target), _lib.ptr(weight), N, 0, 0.0, _lib.ptr(ws),
+                  nbytes, stream)
+        _lib.call("tp3d_kabsch_solve", N, 0, 1, _lib.ptr(T), _lib.ptr(ws), nbytes, stream)
+    return T
+
+
+def ransac_pose(xyz, xyz_target, threshold, num_iterations=80000, ransac_n=4, refine=1, samples=None, generator=None):
+    """RANSAC over the correspondences xyz[i] <-> xyz_target[i], both (N, 3), N >= 3 (open3d's
+    registration_ransac_based_on_correspondence as utils/registration.py:141-163 calls it): `num_iterations` hypotheses
+    from `ransac_n` correspondences each (samples (H, n) int64, default torch.randint(0, N, (num_iterations, ransac_n))
+    on the device with `generator`), scored as in ransac_score; the best is the one with the highest count and among equal
+    counts the LOWEST index -- an integer rule, where open3d compares the inlier RMSE of equal counts; then `refine`
+    rounds of Kabsch over the inliers of the current pose (fewer than 3 inliers leave the pose as it is).
+
+    Returns (T (4, 4) fp32, stats): stats is a dict of device scalars, `best` (int64, the chosen hypothesis),
+    `best_count` (int32, its count), `inliers` (int64, under T, distances in double), `fitness` = inliers / N and
+    `inlier_rmse` = sqrt(sum d^2 / inliers) (float64; 0 without inliers).  A fixed sequence of launches: the inlier set
+    is never compacted and the host reads nothing back."""
+    dev, xyz, xyz_target = _correspondences(xyz, xyz_target, "ransac_pose")
+    N = xyz.shape[0]
+    samples = _ransac_samples(samples, N, num_iterations, ransac_n, dev, generator)
+    H, n = samples.shape
+    ws, nbytes = _ransac_workspace(N, H, dev)
+    counts = torch.empty((H,), dtype=torch.int32, device=dev)
+    T = torch.empty((4, 4), dtype=torch.float32, device=dev)
+    stream = _lib.stream_ptr(dev)
+    thr = float(threshold)
+    cloud = (_lib.ptr(xyz), _lib.ptr(xyz_target))
+    with _lib.on_device(dev):
+        _lib.call("tp3d_ransac_score_f32", *cloud, N, _lib.ptr(samples), H, n, thr, None, _lib.ptr(counts), _lib.ptr(ws), nbytes,
+                  stream)
+        _lib.call("tp3d_ransac_select", *cloud, N, _lib.ptr(samples), H, n, _lib.ptr(counts), _lib.ptr(ws), nbytes, stream)
+        for _ in range(int(refine)):
+            _lib.call("tp3d_kabsch_accumulate_f32", *cloud, None, N, 1, thr, _lib.ptr(ws), nbytes, stream)
+            _lib.call("tp3d_kabsch_solve", N, 1, 1, None, _lib.ptr(ws), nbytes, stream)
+        _lib.call("tp3d_kabsch_accumulate_f32", *cloud, None, N, 1, thr, _lib.ptr(ws), nbytes, stream)
+        _lib.call("tp3d_kabsch_solve", N, 1, 0, _lib.ptr(T), _lib.ptr(ws), nbytes, stream)
+    state = ws[:32 * 8].view(torch.float64).clone()  # (the workspace is reused by the next call)
+    inliers = state[15]
+    stats = {"best": state[13].long(), "best_count": state[14].to(torch.int32), "inliers": inliers.long(),
+             "fitness": inliers / N,
+             "inlier_rmse": torch.sqrt(state[16] / torch.clamp(inliers, min=1.0))}
+    return T, stats
 
 
 # ------------------------------------------------------------------------------------------------ PointNet's per-cloud rows
