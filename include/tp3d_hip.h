@@ -969,6 +969,58 @@ int tp3d_instance_ap_match(const int64_t *order, const int64_t *cls, const int64
                            const int64_t *size, const int64_t *inter_cls, const int64_t *col_cls, const int64_t *gt_size,
                            int64_t G, double threshold, uint8_t *taken, uint8_t *tp, void *stream);
 
+/* Data transforms (csrc/transforms.hip)
+ *                       [core/data_transform/transforms.py, grid_transform.py:169-226]
+ * Region cut: which rows of pos (N, 3) lie in each of B regions of one kind.  Integer counters and plain stores, no float
+ * atomics, bit-equal repeats, nothing of size N * B in memory: a count pass writes one int per (region, tile of
+ * tp3d_region_tile_rows() rows), one block scan turns them into offsets, the emit pass orders the rows of a tile by
+ * ballot and prefix, so every list is ascending.
+ *   kind   0 sphere     d2 < r^2,  d2 = (dx dx + dy dy) + dz dz, d = p - c, r = param[b][0]
+ *          1 cylinder   as the sphere with d2 = dx dx + dy dy
+ *          2 box        |q_i| < param[b][i] for i = 0, 1, 2, q = R d (rot (B, 3, 3) row-major, null: q = d)
+ *          3 ellipsoid  ((qx qx) / (a a) + (qy qy) / (b b)) + (qz qz) / (c c) < 1, (a, b, c) = param[b]
+ *          4 mask       mask[row] != 0 (keep mode only, B = 0, no pos)
+ *     The fp32 inputs are promoted to double, differences first, then products, sums left to right, one rounding per
+ *     operation (no fma): a numpy float64 restatement is bit-equal.
+ *   flags  1 closed: <= in place of <;  2 skip_zero: a row with d2 == 0 is outside (d2 of its kind; box and ellipsoid
+ *          use the sphere's);  4 align_origin: pos_out has the fp32 centre subtracted in fp32 (x, y only for a cylinder)
+ *   mode   0 each: start (B + 1), index / batch (capacity) / pos_out (capacity, 3): region b owns the entries
+ *            start[b] .. start[b + 1]: its rows ascending, its id, and their positions.  batch, pos_out may be null.
+ *          1 keep: one ascending list of the rows that lie in NO region (kind 4: whose mask byte is set); start = [0, T];
+ *            seg_out (S + 1) = the kept rows below seg[s], the per-scene offsets of the kept rows (null: not wanted).
+ *   seg (S + 1), scene (B): region b looks only at rows seg[scene[b]] .. seg[scene[b] + 1] (a scene outside [0, S)
+ *     holds none) and its workgroups read no other tile; scene null: every row.
+ *   tp3d_region_count_f32 fills the workspace and writes start and status = [T, T > capacity] (capacity < 0: no bound;
+ *     T = all entries).  tp3d_region_emit_f32 takes the same arguments and workspace and writes the entries below
+ *     `capacity`; after an overflow the lists are cut there (nothing is written past the buffers) and seg_out is zero.
+ *   N <= 2^31 - 1 and N * B <= 2^31 - 1 in each mode (TP3D_E_TOOBIG beyond): the offsets are ints.
+ * Elastic distortion of a ragged batch.  Cloud b owns a noise grid dims[b] = (d0, d1, d2) cells of 3 channels, C order,
+ * at floats goff[b] .. goff[b + 1] of `noise`; total = goff[B].
+ *   tp3d_elastic_blur_f32: `rounds` rounds of the 3-tap box blur along axis 0, 1, 2 with zero padding, in place (tmp:
+ *     `total` floats).  A pass sums the taps in ascending order in double over the fp32 weight float(1) / float(3) and
+ *     rounds once to fp32: scipy.ndimage.convolve(mode="constant") on float32 input.
+ *   tp3d_elastic_apply_f32: out = fp32(pos + interp(pos) * magnitude) in double; interp is trilinear over the axes
+ *     axes[b][d] = (start, step, stop) doubles, value i = i * step + start, the last one = stop (numpy.linspace); the
+ *     interval is the one with grid[i] <= x < grid[i + 1] (the last closed), the eight corners are summed in the order
+ *     and with the weight products ((1 w_x) w_y) w_z of scipy's RegularGridInterpolator; a row outside the axes of its
+ *     cloud, or of no cloud of seg (B + 1), is copied. */
+int tp3d_region_tile_rows(void);
+size_t tp3d_region_workspace_bytes(int64_t N, int64_t B, int mode);
+int tp3d_region_count_f32(const float *pos, int64_t N, const int64_t *seg, int64_t S, int kind, int mode, int flags,
+                          const float *centre, const float *param, const float *rot, const int64_t *scene,
+                          const uint8_t *mask, int64_t B, int64_t capacity, int64_t *start, int64_t *status, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int tp3d_region_emit_f32(const float *pos, int64_t N, const int64_t *seg, int64_t S, int kind, int mode, int flags,
+                         const float *centre, const float *param, const float *rot, const int64_t *scene,
+                         const uint8_t *mask, int64_t B, int64_t capacity, const int64_t *status, int64_t *index,
+                         int64_t *batch, float *pos_out, int64_t *seg_out, const void *workspace, size_t workspace_bytes,
+                         void *stream);
+int tp3d_elastic_blur_f32(float *noise, float *tmp, const int32_t *dims, const int64_t *goff, int64_t B, int64_t total,
+                          int rounds, void *stream);
+int tp3d_elastic_apply_f32(const float *pos, const int64_t *seg, int64_t B, int64_t N, const float *noise,
+                           const int32_t *dims, const int64_t *goff, const double *axes, double magnitude, float *out,
+                           void *stream);
+
 /* =====================================================================================================
  * Launch plans (host arithmetic only, no device work): what an entry point WILL do for given sizes -- how it
  * splits the rows, how many partial rows it writes, how it carves its workspace.  tests/test_plans_cpu.py sweeps

@@ -9,10 +9,14 @@ Mirrors the names, positional order, return values and error behaviour the refer
   grouping_operation     <- torch_points3d/modules/pointnet2/dense.py:38,45
 
 Tensors must live on a ROCm device: there is deliberately no CPU or eager-PyTorch fallback, a CPU
-tensor (or a missing libtp3d_hip.so) raises.
+tensor (or a missing libtp3d_hip.so) raises.  The one exception is the batch builder at the end of this file
+(region_cut, mask_compact, elastic_distort): it must also run inside DataLoader workers, so CPU tensors go to a
+numpy restatement of the same arithmetic there; device tensors always go to the kernels.
 """
+import collections
 import weakref
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1734,3 +1738,381 @@ def instance_ap_match(order, cls, cloud, valid, size, inter_cls, col_cls, gt_siz
                       _lib.ptr(size), _lib.ptr(inter_cls), _lib.ptr(col_cls), _lib.ptr(gt_size), G, float(threshold),
                       _lib.ptr(taken), _lib.ptr(tp), _lib.stream_ptr(dev))
     return tp.bool()
+
+
+# ------------------------------------------------------------------------------------------- data transforms (csrc/transforms.hip)
+# Unlike the searches above these three take CPU tensors too (a DataLoader worker, the CPU tests): a numpy restatement
+# of the same arithmetic in this file serves them, as seg_metrics.py does for the metrics.  Device tensors always go to
+# the kernels.
+REGION_KINDS = {"sphere": 0, "cylinder": 1, "box": 2, "ellipsoid": 3, "mask": 4}
+_REGION_EACH, _REGION_KEEP = 0, 1
+REGION_MAX_ROWS = (1 << 31) - 1  # rows, and rows x regions in `each` mode: the tile offsets are ints
+
+# start (B + 1,), index (T,), batch (T,), pos (T, 3) or None, seg (S + 1,) or None, status (2,) = [T, overflow]
+RegionCut = collections.namedtuple("RegionCut", "start index batch pos seg status")
+
+
+def region_tile_rows():
+    """rows of one tile of the region kernels (tp3d_region_tile_rows)"""
+    return _lib.load().tp3d_region_tile_rows()
+
+
+def _region_params(centre, param, rot, scene, kind):
+    if kind not in REGION_KINDS or kind == "mask":
+        raise ValueError("kind must be one of sphere, cylinder, box, ellipsoid (a mask goes to mask_compact)")
+    centre = torch.as_tensor(centre)
+    if centre.dim() == 1:
+        centre = centre.unsqueeze(0)
+    if centre.dim() != 2 or centre.shape[1] not in (2, 3) or (centre.shape[1] == 2 and kind != "cylinder"):
+        raise ValueError("centre must be (B, 3) ((B, 2) for cylinders as well)")
+    B = centre.shape[0]
+    centre = centre.to(torch.float32)
+    if centre.shape[1] == 2:
+        centre = torch.cat([centre, torch.zeros((B, 1), dtype=torch.float32, device=centre.device)], 1)
+    if isinstance(param, (int, float)):  # a fill on the centres' device: no host-to-device copy to wait for
+        param = torch.full((B, 3), float(param), dtype=torch.float32, device=centre.device)
+    param = torch.as_tensor(param, dtype=torch.float32, device=centre.device)
+    if param.dim() == 0:
+        param = param.expand(B, 3)
+    elif param.dim() == 1 and param.shape[0] == 3 and kind in ("box", "ellipsoid"):
+        param = param.unsqueeze(0).expand(B, 3)
+    elif param.dim() == 1:
+        param = param.unsqueeze(1).expand(param.shape[0], 3)
+    elif param.dim() == 2 and param.shape[1] == 1:
+        param = param.expand(param.shape[0], 3)
+    if tuple(param.shape) != (B, 3):
+        raise ValueError("param must be a number, (B,), (B, 1) or (B, 3), got %s for %d regions" % (tuple(param.shape), B))
+    if rot is not None:
+        rot = torch.as_tensor(rot, dtype=torch.float32, device=centre.device)
+        if rot.dim() == 2:
+            rot = rot.unsqueeze(0).expand(B, 3, 3)
+        if tuple(rot.shape) != (B, 3, 3):
+            raise ValueError("rot must be (B, 3, 3)")
+        rot = rot.contiguous()
+    if scene is not None:
+        scene = torch.as_tensor(scene, device=centre.device)
+        if scene.dim() != 1 or scene.numel() != B:
+            raise ValueError("scene must name one scene per region")
+        scene = _i64(scene)
+    return centre.contiguous(), param.contiguous(), rot, scene, B
+
+
+def region_holds_numpy(pos, centre, param, rot, kind, closed, skip_zero):
+    """bool (N,): the rows of pos (N, 3) fp32 inside ONE region -- the predicate of csrc/transforms.hip in numpy float64:
+    fp32 inputs promoted, differences first, then products, sums left to right."""
+    p = np.asarray(pos, dtype=np.float32).astype(np.float64).reshape(-1, 3)
+    c = np.asarray(centre, dtype=np.float32).astype(np.float64)
+    h = np.asarray(param, dtype=np.float32).astype(np.float64)
+    dx, dy, dz = p[:, 0] - c[0], p[:, 1] - c[1], p[:, 2] - c[2]
+    planar = dx * dx + dy * dy
+    d2 = planar if kind == "cylinder" else planar + dz * dz
+    if kind in ("sphere", "cylinder"):
+        r2 = h[0] * h[0]
+        inside = d2 <= r2 if closed else d2 < r2
+    else:
+        qx, qy, qz = dx, dy, dz
+        if rot is not None:
+            R = np.asarray(rot, dtype=np.float32).astype(np.float64)
+            qx = (R[0, 0] * dx + R[0, 1] * dy) + R[0, 2] * dz
+            qy = (R[1, 0] * dx + R[1, 1] * dy) + R[1, 2] * dz
+            qz = (R[2, 0] * dx + R[2, 1] * dy) + R[2, 2] * dz
+        if kind == "box":
+            q = np.abs(np.stack([qx, qy, qz], 1))
+            inside = (q <= h).all(1) if closed else (q < h).all(1)
+        else:
+            v = ((qx * qx) / (h[0] * h[0]) + (qy * qy) / (h[1] * h[1])) + (qz * qz) / (h[2] * h[2])
+            inside = v <= 1.0 if closed else v < 1.0
+    if skip_zero:
+        inside = inside & (d2 != 0.0)
+    return inside
+
+
+def _cut_to_capacity(parts, capacity):
+    T = int(parts[0].shape[0])
+    status = torch.tensor([T, int(capacity is not None and T > int(capacity))], dtype=torch.int64)
+    if capacity is not None:
+        parts = [None if t is None else t[:int(capacity)] for t in parts]
+    return parts, status
+
+
+def region_cut_numpy(pos, centre, param, rot, scene, seg, kind, closed, skip_zero, mode, align_origin, capacity, with_pos):
+    """`region_cut` on the host (CPU tensors in, CPU tensors out)"""
+    P = pos.detach().to(torch.float32).numpy().reshape(-1, 3)
+    N, B = P.shape[0], centre.shape[0]
+    C, H = centre.numpy(), param.numpy()
+    R = None if rot is None else rot.numpy()
+    segn = None if seg is None else seg.numpy().astype(np.int64)
+    rows = np.arange(N, dtype=np.int64)
+    masks = []
+    for b in range(B):
+        m = region_holds_numpy(P, C[b], H[b], None if R is None else R[b], kind, closed, skip_zero)
+        if scene is not None:
+            s = int(scene[b])
+            lo, hi = (int(segn[s]), int(segn[s + 1])) if 0 <= s < segn.shape[0] - 1 else (0, 0)
+            m = m & (rows >= lo) & (rows < hi)
+        masks.append(m)
+    if mode == "outside_all":
+        keep = np.ones(N, dtype=bool)
+        for m in masks:
+            keep &= ~m
+        return _mask_compact_numpy(keep, segn, capacity)
+    lists = [rows[m] for m in masks]
+    start = np.zeros(B + 1, dtype=np.int64)
+    start[1:] = np.cumsum([len(l) for l in lists])
+    index = np.concatenate(lists) if B else np.zeros(0, dtype=np.int64)
+    batch = np.repeat(np.arange(B, dtype=np.int64), [len(l) for l in lists]) if B else np.zeros(0, dtype=np.int64)
+    out = None
+    if with_pos:
+        out = P[index].copy()
+        if align_origin and index.shape[0]:
+            c = C[batch].copy()
+            if kind == "cylinder":
+                c[:, 2] = 0
+            out = out - c  # fp32
+    parts, status = _cut_to_capacity([torch.from_numpy(index), torch.from_numpy(batch),
+                                      None if out is None else torch.from_numpy(out.reshape(-1, 3))], capacity)
+    return RegionCut(torch.from_numpy(start), parts[0], parts[1], parts[2], None, status)
+
+
+def _mask_compact_numpy(keep, segn, capacity):
+    index = np.nonzero(keep)[0].astype(np.int64)
+    T = index.shape[0]
+    new_seg = None
+    if segn is not None:
+        new_seg = torch.from_numpy(np.searchsorted(index, np.maximum(segn, 0), side="left").astype(np.int64))
+    (index_t,), status = _cut_to_capacity([torch.from_numpy(index)], capacity)
+    if new_seg is not None and int(status[1]):
+        new_seg = torch.zeros_like(new_seg)
+    return RegionCut(torch.tensor([0, T], dtype=torch.int64), index_t, None, None, new_seg, status)
+
+
+def _region_launch(pos, N, seg, kind_id, mode_id, flags, centre, param, rot, scene, mask, B, capacity, with_pos, dev):
+    """count -> (one host read unless a capacity is given) -> emit; returns a RegionCut of device tensors"""
+    if N > REGION_MAX_ROWS or (mode_id == _REGION_EACH and N * B > REGION_MAX_ROWS):
+        raise ValueError("region_cut serves at most 2^31 - 1 rows, and rows x regions in `each` mode: cut in smaller batches")
+    if capacity is not None and not (0 <= int(capacity) <= REGION_MAX_ROWS):
+        raise ValueError("capacity must lie in [0, 2^31)")
+    S = 0 if seg is None else seg.numel() - 1
+    nstart = B + 1 if mode_id == _REGION_EACH else 2
+    start = torch.empty((nstart,), dtype=torch.int64, device=dev)
+    status = torch.empty((2,), dtype=torch.int64, device=dev)
+    nbytes = _lib.load().tp3d_region_workspace_bytes(N, B, mode_id)
+    ws = _lib.workspace("region", nbytes, dev)
+    head = (_lib.ptr(pos), N, _lib.ptr(seg), S, kind_id, mode_id, flags, _lib.ptr(centre), _lib.ptr(param), _lib.ptr(rot),
+            _lib.ptr(scene), _lib.ptr(mask), B)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_region_count_f32", *head, -1 if capacity is None else int(capacity), _lib.ptr(start),
+                  _lib.ptr(status), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+    cap = int(status[0]) if capacity is None else int(capacity)  # the one device-to-host read
+    # with a capacity the entries behind the lists are never written: they are zero, so that `index` stays a valid
+    # row list for a caller that gathers before it looks at status
+    new = torch.empty if capacity is None else torch.zeros
+    index = new((cap,), dtype=torch.int64, device=dev)
+    each = mode_id == _REGION_EACH
+    batch = new((cap,), dtype=torch.int64, device=dev) if each else None
+    pos_out = new((cap, 3), dtype=torch.float32, device=dev) if (each and with_pos) else None
+    seg_out = torch.empty((S + 1,), dtype=torch.int64, device=dev) if (not each and seg is not None) else None
+    with _lib.on_device(dev):
+        _lib.call("tp3d_region_emit_f32", *head, cap, _lib.ptr(status), _lib.ptr(index), _lib.ptr(batch), _lib.ptr(pos_out),
+                  _lib.ptr(seg_out), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+    return RegionCut(start, index, batch, pos_out, seg_out, status)
+
+
+def region_cut(pos, centre, param, kind="sphere", rot=None, scene=None, seg=None, closed=False, skip_zero=False,
+               mode="each", align_origin=False, capacity=None, with_pos=True):
+    """Cut B regions of one kind out of pos (N, 3): the batch form of the reference's KDTree.query_radius
+    (SphereSampling, CylinderSampling: closed=True), of its `ball_query(mode=1)` dropouts and crops (open) and of the
+    CubeCrop / EllipsoidCrop masks.  Returns a RegionCut.
+
+    kind    "sphere"    d2 < r^2 (closed: <=) with d2 = (dx dx + dy dy) + dz dz, r = param
+            "cylinder"  the same without dz
+            "box"       |q_i| < param_i, q = rot (p - c) (rot (B, 3, 3); None: q = p - c)
+            "ellipsoid" ((qx qx) / (a a) + (qy qy) / (b b)) + (qz qz) / (c c) < 1, param = (a, b, c)
+            in float64 from the fp32 inputs, differences first, sums left to right: `region_holds_numpy` is bit-equal.
+    centre (B, 3), param a number, (B,) or (B, 3); skip_zero drops rows at distance exactly 0 (the `dist > 0` filters of
+    SphereCrop and FixedSphereDropout lose the centre point: kept).
+    seg (S + 1,), scene (B,): region b looks only at the rows seg[scene[b]] : seg[scene[b] + 1] of a resident set of
+    scenes or clouds.
+    mode    "each"         start (B + 1,), index (T,) ascending inside each region, batch (T,) = the region of every
+                           entry (the collated batch vector), pos (T, 3) = pos[index], minus the region's fp32 centre
+                           when align_origin (x, y only for cylinders) -- the reference's `item -= t_center`;
+            "outside_all"  index = the rows that lie in none of the regions (of their own scene, with `scene`),
+                           ascending; seg = the offsets of the kept rows per scene (given seg); start = [0, T].
+    capacity=None: the arrays are exact and the call reads one integer back.  capacity=c: nothing is read back, the
+    arrays have c entries of which the first min(T, c) are meaningful; status (2,) = [T, T > c] on the device.
+    Ascending order is this project's definition (the KDTree returns tree order)."""
+    if mode not in ("each", "outside_all"):
+        raise ValueError("mode must be 'each' or 'outside_all'")
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError("pos must be (N, 3)")
+    centre, param, rot, scene, B = _region_params(centre, param, rot, scene, kind)
+    if scene is not None and seg is None:
+        raise ValueError("scene needs the scene table seg")
+    if seg is not None and (seg.dim() != 1 or seg.numel() < 1):
+        raise ValueError("seg must be (S + 1,)")
+    if pos.device.type != "cuda":
+        return region_cut_numpy(pos, centre.cpu(), param.cpu(), None if rot is None else rot.cpu(),
+                                None if scene is None else scene.cpu(), None if seg is None else seg.cpu(), kind,
+                                bool(closed), bool(skip_zero), mode, bool(align_origin), capacity, with_pos)
+    dev = pos.device
+    centre, param = centre.to(dev), param.to(dev)
+    rot = None if rot is None else rot.to(dev)
+    scene = None if scene is None else scene.to(dev)
+    seg = None if seg is None else _i64(seg.to(dev))
+    flags = int(bool(closed)) | (int(bool(skip_zero)) << 1) | (int(bool(align_origin)) << 2)
+    return _region_launch(_f32(pos), pos.shape[0], seg, REGION_KINDS[kind], _REGION_EACH if mode == "each" else _REGION_KEEP,
+                          flags, centre, param, rot, scene, None, B, capacity, with_pos, dev)
+
+
+def mask_compact(mask, seg=None, capacity=None):
+    """The rows of a ragged batch whose mask entry is set: the batch form of the reference's `apply_mask`.  Returns a
+    RegionCut with index (T,) ascending, seg = the cloud offsets of the kept rows (given seg (B + 1,)), start = [0, T].
+    capacity as in region_cut.  The same count / scan / emit kernels as the region cut, kind `mask`."""
+    if mask.dim() != 1:
+        raise ValueError("mask must be (N,)")
+    if seg is not None and (seg.dim() != 1 or seg.numel() < 1):
+        raise ValueError("seg must be (B + 1,)")
+    if mask.device.type != "cuda":
+        return _mask_compact_numpy(mask.detach().numpy() != 0, None if seg is None else seg.numpy().astype(np.int64), capacity)
+    dev = mask.device
+    m8 = (mask if mask.dtype in (torch.uint8, torch.bool) else mask != 0).contiguous().view(torch.uint8)
+    seg = None if seg is None else _i64(seg.to(dev))
+    return _region_launch(None, mask.numel(), seg, REGION_KINDS["mask"], _REGION_KEEP, 0, None, None, None, None, m8, 0,
+                          capacity, False, dev)
+
+
+# -- elastic distortion
+ElasticGrids = collections.namedtuple("ElasticGrids", "dims goff axes")  # (B, 3) int32, (B + 1,) int64, (B, 3, 3) float64
+
+
+def elastic_grids(cmin, cmax, seg, granularity):
+    """The noise grids of ElasticDistortion.elastic_distortion for clouds with bounds cmin, cmax (B, 3) fp32 on the host:
+    dims = ((pos - min).max // granularity) + 3 in fp32, goff = the float offsets of the (d0, d1, d2, 3) grids in one flat
+    noise tensor, axes[b][d] = (start, step, stop) of numpy.linspace(min - g, min + g (dim - 2), dim) -- the start an fp32
+    difference, the stop a float64 sum, as the reference's numpy expressions make them.  An empty cloud gets 3 cells."""
+    cmin = np.asarray(cmin, dtype=np.float32).reshape(-1, 3)
+    cmax = np.asarray(cmax, dtype=np.float32).reshape(-1, 3)
+    segn = np.asarray(seg, dtype=np.int64)
+    empty = (segn[1:] == segn[:-1])[:, None]
+    cmin, cmax = np.where(empty, np.float32(0), cmin), np.where(empty, np.float32(0), cmax)
+    g32 = np.float32(granularity)
+    dims = ((cmax - cmin) // g32).astype(np.int64) + 3
+    start = (cmin - g32).astype(np.float64)
+    stop = cmin.astype(np.float64) + float(granularity) * (dims - 2)
+    step = (stop - start) / (dims - 1)
+    goff = np.zeros(dims.shape[0] + 1, dtype=np.int64)
+    goff[1:] = np.cumsum(dims.prod(1) * 3)
+    return ElasticGrids(dims.astype(np.int32), goff, np.ascontiguousarray(np.stack([start, step, stop], 2)))
+
+
+def elastic_blur_numpy(noise, rounds=2):
+    """`rounds` rounds of the 3-tap box blur along x, y, z of one (d0, d1, d2, 3) fp32 grid: zero padding, taps ascending,
+    summed in double over the fp32 weight 1/3, rounded to fp32 per pass"""
+    w = np.float64(np.float32(1) / np.float32(3))
+    noise = np.asarray(noise, dtype=np.float32)
+    for _ in range(rounds):
+        for axis in range(3):
+            x = np.moveaxis(noise.astype(np.float64), axis, 0)
+            pad = np.zeros((1,) + x.shape[1:])
+            lo, hi = np.concatenate([pad, x[:-1]]), np.concatenate([x[1:], pad])
+            noise = np.moveaxis((((0.0 + lo * w) + x * w) + hi * w).astype(np.float32), 0, axis)
+    return noise
+
+
+def elastic_apply_numpy(pos, noise, dims, axes, magnitude):
+    """fp32(pos + interp(pos) * magnitude) for ONE cloud in float64: the arithmetic of tp3d_elastic_apply_f32"""
+    p = np.asarray(pos, dtype=np.float32).astype(np.float64).reshape(-1, 3)
+    n = p.shape[0]
+    inside = np.ones(n, dtype=bool)
+    idx, y = [], []
+    for d in range(3):
+        start, step, stop = (float(v) for v in axes[d])
+        m = int(dims[d])
+        grid = np.arange(m, dtype=np.float64) * step + start
+        grid[-1] = stop
+        x = p[:, d]
+        inside &= (x >= grid[0]) & (x <= grid[-1])
+        i = np.clip(np.searchsorted(grid, x, side="right") - 1, 0, m - 2)
+        idx.append(i)
+        y.append((x - grid[i]) / (grid[i + 1] - grid[i]))
+    value = np.zeros((n, 3))
+    g = np.asarray(noise, dtype=np.float32).reshape(int(dims[0]), int(dims[1]), int(dims[2]), 3)
+    for h in range(8):
+        hx, hy, hz = h >> 2, (h >> 1) & 1, h & 1
+        weight = np.ones(n)
+        weight = weight * (y[0] if hx else 1.0 - y[0])
+        weight = weight * (y[1] if hy else 1.0 - y[1])
+        weight = weight * (y[2] if hz else 1.0 - y[2])
+        value = value + g[idx[0] + hx, idx[1] + hy, idx[2] + hz].astype(np.float64) * weight[:, None]
+    value[~inside] = 0.0
+    return (p + value * float(magnitude)).astype(np.float32)
+
+
+def _elastic_noise(noise, grids, generator, dev):
+    total = int(grids.goff[-1])
+    if noise is None:
+        gdev = generator.device if generator is not None else torch.device("cpu")
+        return torch.randn(total, generator=generator, dtype=torch.float32, device=gdev).to(dev)
+    if isinstance(noise, (list, tuple)):
+        noise = torch.cat([torch.as_tensor(t, dtype=torch.float32).reshape(-1) for t in noise]) if noise else torch.zeros(0)
+    noise = torch.as_tensor(noise, dtype=torch.float32).reshape(-1)
+    if noise.numel() != total:
+        raise ValueError("noise holds %d floats, the grids %s need %d" % (noise.numel(), grids.dims.tolist(), total))
+    return noise.to(dev)
+
+
+def elastic_distort(pos, seg, granularity, magnitude, noise=None, generator=None, return_grids=False):
+    """ElasticDistortion.elastic_distortion (grid_transform.py:193-218) on every cloud of a ragged batch: pos (N, 3) fp32,
+    seg (B + 1,) the cloud offsets.  Per cloud: a noise grid of ((pos - min).max // granularity) + 3 cells per axis and 3
+    channels, two rounds of the 3-tap box blur along x, y, z, trilinear interpolation at pos, pos + interp * magnitude in
+    float64 rounded once to fp32.  The per-cloud bounds come from a device reduction (segment_max) and are read once,
+    because the noise must be allocated; nothing else is read back.
+
+    noise: the raw standard-normal grids, one flat tensor of `elastic_grids(...).goff[-1]` floats or a list of per-cloud
+    (d0, d1, d2, 3) arrays; None draws it with torch.randn(generator=generator).  The kernels draw nothing."""
+    if pos.dim() != 2 or pos.shape[1] != 3 or seg.dim() != 1 or seg.numel() < 1:
+        raise ValueError("pos must be (N, 3) and seg (B + 1,)")
+    B = seg.numel() - 1
+    gpu = pos.device.type == "cuda"
+    p32 = _f32(pos)
+    if B == 0 or pos.shape[0] == 0:
+        out = p32.clone()
+        return (out, elastic_grids(np.zeros((B, 3)), np.zeros((B, 3)), seg.cpu().numpy(), granularity)) if return_grids else out
+    if gpu:
+        seg = _i64(seg.to(pos.device))
+        filled = (seg[1:] > seg[:-1]).float().unsqueeze(1).expand(B, 3)  # which clouds have rows travels with the bounds
+        read = torch.stack([-segment_max(-p32, seg), segment_max(p32, seg), filled]).cpu().numpy()  # the one host read
+        bounds = read[:2]
+        seg_host = np.concatenate([[0], np.cumsum(read[2, :, 0] > 0)])  # stands for seg: only emptiness is used
+    else:
+        seg_host = seg.numpy().astype(np.int64)
+        P = p32.numpy()
+        bounds = np.zeros((2, B, 3), dtype=np.float32)
+        for b in range(B):
+            if seg_host[b + 1] > seg_host[b]:
+                bounds[0, b], bounds[1, b] = P[seg_host[b]:seg_host[b + 1]].min(0), P[seg_host[b]:seg_host[b + 1]].max(0)
+    grids = elastic_grids(bounds[0], bounds[1], seg_host, granularity)
+    noise = _elastic_noise(noise, grids, generator, pos.device)
+    if gpu:
+        dev = pos.device
+        noise = noise.clone()
+        tmp = torch.empty_like(noise)
+        dims, goff = torch.from_numpy(grids.dims).to(dev), torch.from_numpy(grids.goff).to(dev)
+        axes = torch.from_numpy(grids.axes).to(dev)
+        out = torch.empty_like(p32)
+        with _lib.on_device(dev):
+            _lib.call("tp3d_elastic_blur_f32", _lib.ptr(noise), _lib.ptr(tmp), _lib.ptr(dims), _lib.ptr(goff), B,
+                      noise.numel(), 2, _lib.stream_ptr(dev))
+            _lib.call("tp3d_elastic_apply_f32", _lib.ptr(p32), _lib.ptr(seg), B, p32.shape[0], _lib.ptr(noise), _lib.ptr(dims),
+                      _lib.ptr(goff), _lib.ptr(axes), float(magnitude), _lib.ptr(out), _lib.stream_ptr(dev))
+    else:
+        P, Nz = p32.numpy(), noise.numpy()
+        res = P.copy()
+        for b in range(B):
+            lo, hi = int(seg_host[b]), int(seg_host[b + 1])
+            if hi > lo:
+                d = grids.dims[b]
+                g = elastic_blur_numpy(Nz[grids.goff[b]:grids.goff[b + 1]].reshape(d[0], d[1], d[2], 3))
+                res[lo:hi] = elastic_apply_numpy(P[lo:hi], g, d, grids.axes[b], magnitude)
+        out = torch.from_numpy(res)
+    return (out, grids) if return_grids else out
