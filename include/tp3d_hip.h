@@ -1022,6 +1022,37 @@ int tp3d_elastic_apply_f32(const float *pos, const int64_t *seg, int64_t B, int6
                            void *stream);
 
 /* =====================================================================================================
+ * FPFH descriptors (csrc/fpfh.hip): open3d's estimate_normals + compute_fpfh_feature over a hybrid (radius, max_nn)
+ * search, as restated in float64 numpy by torch_points3d_amd/fpfh.py -- that file is the definition of every rule.
+ * Ragged batches: seg_x (clouds + 1) row offsets of x, batch_y the cloud of every query.
+ *   tp3d_hybrid_search_f32: of the rows of the query's cloud with (dx*dx + dy*dy) + dz*dz < radius*radius in fp32 (the
+ *     membership of tp3d_ball_query_partial_dense_f32), the max_nn <= TP3D_FPFH_MAX_NN smallest by (dist2, index), in that
+ *     order: idx (Nq, max_nn) global rows, dist2 (Nq, max_nn), both padded with -1, and count (Nq).  Served from the grid
+ *     (cell edge = radius) for every max_nn; M <= 2^31 - 1.
+ *   tp3d_fpfh_normals_f32: per row the unit eigenvector of the smallest eigenvalue of the covariance of its count
+ *     neighbours (mean and covariance in double, slot order; cyclic Jacobi), (0, 0, 1) for count < 3; signed towards
+ *     viewpoint (N, 3) or, with viewpoint null, so that its largest component (lowest axis on ties) is positive.
+ *   tp3d_spfh_counts_f32: counts (N, 33): how many of the slots 1 .. count - 1 of a row fall into each of the 11 bins of
+ *     the three Darboux-frame features; integer adds only.  The angle bin is decided against the ten edge directions of
+ *     tp3d_fpfh_edge_table (table[20] = (cos, sin) of -pi + 2 pi e / 11, e = 1 .. 10; a host function), not by atan2.
+ *   tp3d_fpfh_f32: for r < R the row i = rows[r] (rows null: i = r): out[b] = (sum[b / 11] != 0 ? acc[b] * 100 /
+ *     sum[b / 11] : 0) + spfh_i[b], acc and sum over the slots 1 .. count - 1 with d2 != 0 of spfh_j[b] / d2 in double,
+ *     spfh_j = counts_j * (100 / (count_j - 1)); out64 (R, 33) and / or out32 = its one rounding.
+ * ===================================================================================================== */
+#define TP3D_FPFH_MAX_NN 256
+int tp3d_fpfh_edge_table(double *table);
+size_t tp3d_hybrid_search_workspace_bytes(int num_clouds, int64_t rows, int max_cloud_points);
+int tp3d_hybrid_search_f32(const float *x, const float *y, const int64_t *batch_y, const int64_t *seg_x, int num_clouds,
+                           int max_cloud_points, int64_t M, int64_t Nq, float radius, int max_nn, int32_t *idx,
+                           float *dist2, int32_t *count, void *workspace, size_t workspace_bytes, void *stream);
+int tp3d_fpfh_normals_f32(const float *pos, const int32_t *idx, const int32_t *count, int64_t N, int max_nn,
+                          const float *viewpoint, float *normals, void *stream);
+int tp3d_spfh_counts_f32(const float *pos, const float *normals, const int32_t *idx, const int32_t *count, int64_t N,
+                         int max_nn, int32_t *counts, void *stream);
+int tp3d_fpfh_f32(const float *pos, const int32_t *idx, const int32_t *count, const int32_t *counts, const int64_t *rows,
+                  int64_t R, int64_t N, int max_nn, double *out64, float *out32, void *stream);
+
+/* =====================================================================================================
  * Launch plans (host arithmetic only, no device work): what an entry point WILL do for given sizes -- how it
  * splits the rows, how many partial rows it writes, how it carves its workspace.  tests/test_plans_cpu.py sweeps
  * them against the workspace-size queries above, so that "the extent a kernel writes <= the size the caller was

@@ -158,6 +158,51 @@ def get_matches(feat_source, feat_target, sym=False):
     return matches
 
 
+def _feature_nearest(a, b):
+    """for every row of a the row of b nearest in feature space: feature_nn on the device, a float64 argmin (the lowest
+    index among equal distances) for CPU tensors"""
+    if a.device.type != "cpu":
+        return tp.feature_nn(a, b)[1]
+    A, B = a.detach().double(), b.detach().double()
+    return torch.cat([((A[r0:r0 + 1024, None, :] - B[None]) ** 2).sum(-1).argmin(1) for r0 in range(0, len(A), 1024)])
+
+
+def compute_matches(feature_source, feature_target, kp_source, kp_target, sym=False):
+    """descriptor_matcher.py:40-59 of the reference's test_registration_scripts: every target keypoint with the source
+    keypoint nearest in feature space; sym=True keeps the mutual nearest neighbours only.  Returns (new_kp_source,
+    new_kp_target), row-aligned (M, 3), on the inputs' device (the script's KDTree queries are feature_nn here; its
+    unused `ratio` argument is dropped)."""
+    near_t = _feature_nearest(feature_target, feature_source)  # target row -> source row
+    keep = torch.arange(len(near_t), device=near_t.device)
+    if sym:
+        near_s = _feature_nearest(feature_source, feature_target)
+        keep = keep[near_s[near_t] == keep]
+    return kp_source[near_t[keep]], kp_target[keep]
+
+
+def compute_dists(kp_source, kp_target, trans):
+    """descriptor_matcher.py:62-68: |kp_source - (R kp_target + t)| per matched pair under the (4, 4) pose `trans`"""
+    trans = torch.as_tensor(trans, dtype=kp_target.dtype, device=kp_target.device)
+    return torch.linalg.norm(kp_source - (kp_target @ trans[:3, :3].T + trans[:3, 3]), dim=1)
+
+
+def compute_mean_correct_matches(dist, list_tau, is_leq=True):
+    """descriptor_matcher.py:71-81: for every tau the share of entries below it (is_leq) or above it, over axis 0 of
+    dist; a (len(list_tau), ...) tensor on dist's device"""
+    dist = torch.as_tensor(dist)
+    return torch.stack([((dist < tau) if is_leq else (dist > tau)).to(torch.float64).mean(0) for tau in list_tau])
+
+
+def feature_match_recall(pairs, list_tau1=(0.1,), list_tau2=(0.05,)):
+    """The feature-match recall of descriptor_matcher.py:121-142 over a list of pairs (feat_s, feat_t, kp_s, kp_t, T_gt):
+    per pair the share of matches closer than tau_1 under T_gt, then for every tau_2 the share of pairs whose share
+    exceeds it.  Returns (recall (len(list_tau2), len(list_tau1)), frac_correct (pairs, len(list_tau1))), float64 on the
+    inputs' device; nothing is read back."""
+    frac = torch.stack([compute_mean_correct_matches(compute_dists(*compute_matches(fs, ft, ks, kt), T), list_tau1)
+                        for fs, ft, ks, kt, T in pairs])
+    return compute_mean_correct_matches(frac, list_tau2, is_leq=False), frac
+
+
 def estimate_transfo(xyz, xyz_target):
     """Kabsch (utils/registration.py:24-43): the (4, 4) pose that maps xyz onto xyz_target in the least-squares sense"""
     assert xyz.shape == xyz_target.shape

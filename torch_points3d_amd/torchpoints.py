@@ -23,8 +23,8 @@ from . import _lib
 
 __all__ = ["furthest_point_sample", "ball_query", "three_nn", "three_interpolate", "grouping_operation"]
 # (message-passing side: fps_quota, fps_ragged, radius_edges, pointconv_rows, segment_max, rsconv_relation_rows,
-# rsconv_msgmax; PointGroup's clustering: ClusterSet, region_grow_csr; registration: feature_nn, gather_rows, fgr, ransac_score, kabsch, ransac_pose --
-# further down)
+# rsconv_msgmax; PointGroup's clustering: ClusterSet, region_grow_csr; registration: feature_nn, gather_rows, fgr, ransac_score, kabsch, ransac_pose;
+# FPFH: hybrid_search, estimate_normals, normals_from_neighbours, spfh_counts, fpfh -- further down)
 
 
 def _dev(*tensors):
@@ -2116,3 +2116,174 @@ def elastic_distort(pos, seg, granularity, magnitude, noise=None, generator=None
                 res[lo:hi] = elastic_apply_numpy(P[lo:hi], g, d, grids.axes[b], magnitude)
         out = torch.from_numpy(res)
     return (out, grids) if return_grids else out
+
+
+# ------------------------------------------------------------------------------------------------ FPFH (csrc/fpfh.hip)
+FPFH_MAX_NN = _lib.CONSTANTS["TP3D_FPFH_MAX_NN"]  # largest max_nn of the hybrid search
+
+
+def _np(t):
+    return None if t is None else t.detach().cpu().numpy()
+
+
+def _cloud_segments(batch, n, dev):
+    """(batch vector, seg, clouds, largest cloud) of n rows; batch None: one cloud, nothing read back"""
+    if batch is None:
+        return (torch.zeros(n, dtype=torch.int64, device=dev), torch.tensor([0, n], dtype=torch.int64, device=dev), 1, n)
+    b = _i64(batch)
+    if b.numel() != n:
+        raise ValueError("batch vectors must have one entry per point")
+    return (b,) + tuple(_segments(b))
+
+
+def _neighbour_table(pos, idx, count, what):
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError("%s: pos must be (N, 3)" % what)
+    N = pos.shape[0]
+    if idx.dim() != 2 or idx.shape[0] != N or tuple(count.shape) != (N,) or idx.shape[1] < 1:
+        raise ValueError("%s: idx must be (N, max_nn) and count (N,), as hybrid_search returns them" % what)
+    return N, idx.shape[1]
+
+
+def _i32(t):
+    return (t if t.dtype == torch.int32 else t.to(torch.int32)).contiguous()
+
+
+def hybrid_search(x, y, radius, max_nn, batch_x=None, batch_y=None):
+    """open3d's KDTreeSearchParamHybrid(radius, max_nn) for every row of y (Nq, 3) over the rows of x (M, 3) of its own
+    cloud (sorted batch vectors; None = one cloud): of the rows with (dx*dx + dy*dy) + dz*dz < radius*radius in fp32
+    (ball_query's membership) the max_nn smallest by (dist2, index), in that order -- the rows of knn(max_nn, ...) cut at
+    the radius.  Returns (idx (Nq, max_nn) int32 global rows, dist2 (Nq, max_nn) fp32, count (Nq,) int32), padded with
+    -1.  For x is y slot 0 is the point itself (or a coincident point of lower index).  Device tensors are served from
+    the search grid with the radius as its cell edge for every max_nn <= 256 (csrc/fpfh.hip); CPU tensors by the numpy
+    restatement of fpfh.py."""
+    max_nn = int(max_nn)
+    if not 1 <= max_nn <= FPFH_MAX_NN:
+        raise ValueError("hybrid_search: max_nn must lie in [1, %d], got %d" % (FPFH_MAX_NN, max_nn))
+    if not float(radius) > 0.0:
+        raise ValueError("hybrid_search: the radius must be positive")
+    if x.dim() != 2 or y.dim() != 2 or x.shape[1] != 3 or y.shape[1] != 3:
+        raise ValueError("hybrid_search expects x (M, 3) and y (Nq, 3)")
+    if x.device.type == "cpu" and y.device.type == "cpu":
+        from . import fpfh as _fpfh
+        return tuple(torch.from_numpy(a) for a in _fpfh.hybrid_search_numpy(
+            _np(_f32(x)), _np(_f32(y)), radius, max_nn, _np(batch_x), _np(batch_y)))
+    dev = _dev(x, y)
+    same = x is y and batch_x is batch_y
+    x = _f32(x)
+    y = x if same else _f32(y)
+    bx, seg, nclouds, nmax = _cloud_segments(batch_x, x.shape[0], dev)
+    by = bx if same else (torch.zeros(y.shape[0], dtype=torch.int64, device=dev) if batch_y is None else _i64(batch_y))
+    if by.numel() != y.shape[0]:
+        raise ValueError("batch vectors must have one entry per point")
+    Nq = y.shape[0]
+    idx = torch.empty((Nq, max_nn), dtype=torch.int32, device=dev)
+    d2 = torch.empty((Nq, max_nn), dtype=torch.float32, device=dev)
+    count = torch.empty((Nq,), dtype=torch.int32, device=dev)
+    if Nq == 0:
+        return idx, d2, count
+    if nclouds == 0:
+        return idx.fill_(-1), d2.fill_(-1.0), count.zero_()
+    nbytes = _lib.load().tp3d_hybrid_search_workspace_bytes(nclouds, x.shape[0], max(nmax, 1))
+    if nbytes == 0:
+        raise ValueError("hybrid_search: %d clouds of up to %d points are not served" % (nclouds, nmax))
+    ws = _lib.workspace("grid", nbytes, dev)
+    _grid_owner.pop((dev.index, _lib.stream_ptr(dev)), None)  # the shared grid workspace is overwritten
+    with _lib.on_device(dev):
+        _lib.call("tp3d_hybrid_search_f32", _lib.ptr(x), _lib.ptr(y), _lib.ptr(by), _lib.ptr(seg), nclouds, nmax, x.shape[0],
+                  Nq, float(radius), max_nn, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(count), _lib.ptr(ws), nbytes,
+                  _lib.stream_ptr(dev))
+    return idx, d2, count
+
+
+def _point_viewpoint(viewpoint, batch, N, like):
+    """viewpoint (3,) or (clouds, 3) as an fp32 (N, 3) tensor on the device of `like`"""
+    if viewpoint is None:
+        return None
+    vp = torch.as_tensor(viewpoint, dtype=torch.float32).to(like.device).reshape(-1, 3)
+    if vp.shape[0] == 1:
+        return vp.expand(N, 3).contiguous()
+    if batch is None:
+        raise ValueError("estimate_normals: one viewpoint per cloud needs the batch vector")
+    return vp[batch.long().to(like.device)].contiguous()
+
+
+def normals_from_neighbours(pos, idx, count, viewpoint=None):
+    """The normal of every row from its neighbour table (hybrid_search with x is y): the unit eigenvector of the smallest
+    eigenvalue of the covariance of its count neighbours, (0, 0, 1) for count < 3; viewpoint (N, 3) fp32 or None, see
+    estimate_normals.  (N, 3) fp32."""
+    N, K = _neighbour_table(pos, idx, count, "normals_from_neighbours")
+    if pos.device.type == "cpu":
+        from . import fpfh as _fpfh
+        return torch.from_numpy(_fpfh.estimate_normals_numpy(_np(_f32(pos)), _np(idx), _np(count), _np(viewpoint)))
+    dev = _dev(pos, idx, count, viewpoint)
+    pos, idx, count = _f32(pos), _i32(idx), _i32(count)
+    vp = None if viewpoint is None else _f32(viewpoint)
+    if vp is not None and tuple(vp.shape) != (N, 3):
+        raise ValueError("normals_from_neighbours: viewpoint must be (N, 3)")
+    out = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_fpfh_normals_f32", _lib.ptr(pos), _lib.ptr(idx), _lib.ptr(count), N, K, _lib.ptr(vp), _lib.ptr(out),
+                  _lib.stream_ptr(dev))
+    return out
+
+
+def estimate_normals(pos, batch, radius, max_nn, viewpoint=None):
+    """open3d's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) on a ragged batch: pos (N, 3), sorted batch (N,)
+    or None.  With k = the neighbours hybrid_search finds (the point included): k < 3 gives (0, 0, 1); otherwise, in
+    double from the fp32 coordinates, the mean of the neighbours in slot order, the covariance sum (p - m)(p - m)^T / k,
+    and the unit eigenvector of its smallest eigenvalue by cyclic Jacobi sweeps, rounded once to fp32.  Sign: with
+    viewpoint ((3,) or (clouds, 3)) the normal is flipped when n . (viewpoint - p) < 0; without it so that its component
+    of largest magnitude, the lowest axis on ties, is positive (open3d leaves the eigen solver's sign).  (N, 3) fp32."""
+    idx, _, count = hybrid_search(pos, pos, radius, max_nn, batch, batch)
+    return normals_from_neighbours(pos, idx, count, _point_viewpoint(viewpoint, batch, pos.shape[0], pos))
+
+
+def spfh_counts(pos, normals, idx, count):
+    """(N, 33) int32: for every row of pos (N, 3) with normals (N, 3) the number of its slots 1 .. count - 1 of the
+    neighbour table (idx, count of hybrid_search with x is y; slot 0, the point itself, is skipped as in open3d) that
+    fall into each of the 11 bins of the three Darboux-frame features of open3d's ComputePairFeatures, blocks in
+    open3d's order (angle, v . n2, the cosine of the larger angle).  Pair features in double from the fp32 inputs; the
+    angle bin is decided against ten edge directions, not by atan2, and the swap by |a1| < |a2| (fpfh.py states the
+    rules).  SPFH = counts * 100 / (count - 1).  Integer counts: exact and order-free; the device equals numpy."""
+    N, K = _neighbour_table(pos, idx, count, "spfh_counts")
+    if tuple(normals.shape) != (N, 3):
+        raise ValueError("spfh_counts: normals must be (N, 3)")
+    if pos.device.type == "cpu":
+        from . import fpfh as _fpfh
+        return torch.from_numpy(_fpfh.spfh_counts_numpy(_np(_f32(pos)), _np(_f32(normals)), _np(idx), _np(count)))
+    dev = _dev(pos, normals, idx, count)
+    pos, normals, idx, count = _f32(pos), _f32(normals), _i32(idx), _i32(count)
+    out = torch.empty((N, 33), dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_spfh_counts_f32", _lib.ptr(pos), _lib.ptr(normals), _lib.ptr(idx), _lib.ptr(count), N, K, _lib.ptr(out),
+                  _lib.stream_ptr(dev))
+    return out
+
+
+def fpfh(pos, normals, idx, count, counts, rows=None, dtype=torch.float32):
+    """open3d's compute_fpfh_feature from the SPFH counts of spfh_counts: for every row i of `rows` (int64 rows of pos,
+    e.g. data.keypoints; None: all) and every slot s = 1 .. count_i - 1 with neighbour j and d2 = (dx*dx + dy*dy) + dz*dz
+    != 0 in double, spfh_j[b] / d2 is added into acc[b] and into sum[b // 11], in slot order, bins ascending; out[b] =
+    (sum[b // 11] != 0 ? acc[b] * 100 / sum[b // 11] : 0) + spfh_i[b].  All in double; dtype float32 is its one
+    rounding.  `normals` is not read (the counts hold what they contributed); it keeps open3d's argument order.
+    Returns (R, 33)."""
+    N, K = _neighbour_table(pos, idx, count, "fpfh")
+    if tuple(counts.shape) != (N, 33):
+        raise ValueError("fpfh: counts must be (N, 33), as spfh_counts returns them")
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError("fpfh: dtype must be float32 or float64")
+    if pos.device.type == "cpu":
+        from . import fpfh as _fpfh
+        out = _fpfh.fpfh_numpy(_np(_f32(pos)), _np(idx), _np(count), _np(counts), None if rows is None else _np(rows))
+        return torch.from_numpy(out if dtype == torch.float64 else out.astype(np.float32))
+    dev = _dev(pos, idx, count, counts, rows)
+    pos, idx, count, counts = _f32(pos), _i32(idx), _i32(count), _i32(counts)
+    rows = None if rows is None else _i64(rows).reshape(-1)
+    R = N if rows is None else rows.numel()
+    out = torch.empty((R, 33), dtype=dtype, device=dev)
+    o64, o32 = (_lib.ptr(out), None) if dtype == torch.float64 else (None, _lib.ptr(out))
+    with _lib.on_device(dev):
+        _lib.call("tp3d_fpfh_f32", _lib.ptr(pos), _lib.ptr(idx), _lib.ptr(count), _lib.ptr(counts), _lib.ptr(rows), R, N, K,
+                  o64, o32, _lib.stream_ptr(dev))
+    return out
