@@ -1053,6 +1053,55 @@ int tp3d_fpfh_f32(const float *pos, const int32_t *idx, const int32_t *count, co
                   int64_t R, int64_t N, int max_nn, double *out64, float *out32, void *stream);
 
 /* =====================================================================================================
+ * TSDF fusion (csrc/tsdf.hip): the reference's datasets/registration/fusion.py (TSDFVolume) and utils.py (extract_pcd,
+ * rgbd2pcd), as restated in float64 numpy by torch_points3d_amd/tsdf.py -- that file is the definition of every rule, and
+ * the device equals it bit for bit.  One owner per voxel, plain stores, no atomics of any kind.
+ *   tp3d_tsdf_integrate: F <= TP3D_TSDF_MAX_FRAMES frames (F, H, W) into tsdf, weight (X, Y, Z) fp32, C order, in place.
+ *     One thread per voxel, consecutive threads along z; the frames are applied in order in registers, so every volume
+ *     element is read once and written at most once whatever F is, and the result is bit-equal to F one-frame calls.
+ *     consts (F, TP3D_TSDF_CONSTS) doubles per frame: rows 0 .. 2 of inv(cam_pose) (12), double(fp32(fx, fy, cx, cy)), the
+ *     observation weight.  depth_kind 0: uint16 raw, metres = double(raw) / depth_scale, zeroed above depth_thresh (give
+ *     +inf for none); 1: float64 metres, used as they are.  Per voxel and frame:
+ *       p_a = fp32(o_a + fp32(fp32(voxel_size) * fp32(i_a)));  c_r = ((M_r0 p_x + M_r1 p_y) + M_r2 p_z) + M_r3 in double;
+ *       skip unless c_z > 0;  px = rint(c_x * fx / c_z + cx) (half to even), py likewise; skip unless 0 <= px < W and
+ *       0 <= py < H (in double);  d = depth[py, px]; skip unless d > 0 and diff = d - c_z >= -trunc;
+ *       dist = min(1, diff / trunc);  w_new = fp32(double(w) + obs);
+ *       t = fp32((double(fp32(w * t)) + obs * dist) / double(w_new));  w = w_new.
+ *     X * Y * Z <= (2^31 - 1) * 256 and Y * Z <= 2^31 - 1 (TP3D_E_TOOBIG beyond).
+ *   tp3d_tsdf_surface_count / _emit: the voxels with |t| < tsdf_thresh and w > weight_thresh (fp32 compares) in ascending
+ *     voxel index: pos (capacity, 3) doubles = double(i_a) * voxel_size + double(o_a) and / or index (capacity) flat voxel
+ *     ids (either may be null).  The predicate is evaluated on the fly in both passes over tiles of tp3d_tsdf_tile_rows()
+ *     voxels (count per tile, one block scan, ballot-and-prefix emit: the pieces of the region cut); no mask of volume size
+ *     is written.  _count writes status = [T, T > capacity] (capacity < 0: no bound); _emit writes the entries below
+ *     `capacity` and nothing past them.  N = X * Y * Z <= 2^31 - 1 (TP3D_E_TOOBIG beyond).
+ *   tp3d_depth_unproject_count / _emit: F raw uint16 frames (F, H, W) as one ragged list: start (F + 1); per kept pixel
+ *     ((Z < max_depth) & (Z > 0), Z = double(raw) / depth_scale, ascending pixel index) the world row pos (capacity, 3)
+ *     doubles and pixel (capacity) = f * H * W + y * W + x (either may be null).  consts (F, TP3D_UNPROJECT_CONSTS): rows
+ *     0 .. 2 of the pose (12), K00, K11, K02, K12.  X = ((x + 0.5) - K02) * Z / K00, Y likewise with y, K12, K11;
+ *     pos_a = ((X r_a0 + Y r_a1) + Z r_a2) + t_a.  status and capacity as above; F * H * W <= 2^31 - 1.
+ * ===================================================================================================== */
+#define TP3D_TSDF_MAX_FRAMES 64
+#define TP3D_TSDF_CONSTS 17
+#define TP3D_UNPROJECT_CONSTS 16
+int tp3d_tsdf_tile_rows(void);
+int tp3d_tsdf_integrate(float *tsdf, float *weight, int64_t X, int64_t Y, int64_t Z, float ox, float oy, float oz,
+                        double voxel_size, double trunc, const void *depth, int depth_kind, int F, int H, int W,
+                        const double *consts, double depth_scale, double depth_thresh, void *stream);
+size_t tp3d_tsdf_surface_workspace_bytes(int64_t N);
+int tp3d_tsdf_surface_count(const float *tsdf, const float *weight, int64_t N, float tsdf_thresh, float weight_thresh,
+                            int64_t capacity, int64_t *status, void *workspace, size_t workspace_bytes, void *stream);
+int tp3d_tsdf_surface_emit(const float *tsdf, const float *weight, int64_t X, int64_t Y, int64_t Z, float ox, float oy,
+                           float oz, double voxel_size, float tsdf_thresh, float weight_thresh, int64_t capacity,
+                           double *pos, int64_t *index, const void *workspace, size_t workspace_bytes, void *stream);
+size_t tp3d_depth_unproject_workspace_bytes(int64_t F, int64_t HW);
+int tp3d_depth_unproject_count(const uint16_t *depth, int64_t F, int64_t H, int64_t W, double depth_scale, double max_depth,
+                               int64_t capacity, int64_t *start, int64_t *status, void *workspace, size_t workspace_bytes,
+                               void *stream);
+int tp3d_depth_unproject_emit(const uint16_t *depth, int64_t F, int64_t H, int64_t W, const double *consts,
+                              double depth_scale, double max_depth, int64_t capacity, double *pos, int64_t *pixel,
+                              const void *workspace, size_t workspace_bytes, void *stream);
+
+/* =====================================================================================================
  * Launch plans (host arithmetic only, no device work): what an entry point WILL do for given sizes -- how it
  * splits the rows, how many partial rows it writes, how it carves its workspace.  tests/test_plans_cpu.py sweeps
  * them against the workspace-size queries above, so that "the extent a kernel writes <= the size the caller was

@@ -2287,3 +2287,193 @@ def fpfh(pos, normals, idx, count, counts, rows=None, dtype=torch.float32):
         _lib.call("tp3d_fpfh_f32", _lib.ptr(pos), _lib.ptr(idx), _lib.ptr(count), _lib.ptr(counts), _lib.ptr(rows), R, N, K,
                   o64, o32, _lib.stream_ptr(dev))
     return out
+
+
+# ------------------------------------------------------------------------------------------- TSDF fusion (csrc/tsdf.hip)
+TSDF_MAX_FRAMES = _lib.CONSTANTS["TP3D_TSDF_MAX_FRAMES"]  # frames of one tp3d_tsdf_integrate launch
+TSDF_MAX_VOXELS = (1 << 31) - 1                            # voxels tsdf_surface serves
+
+# pos (T, 3) float64, index (T,) int64 flat voxel ids, status (2,) int64 = [T, overflow]
+TsdfSurface = collections.namedtuple("TsdfSurface", "pos index status")
+# start (F + 1,) int64, pos (T, 3) float64 world rows, pixel (T,) int64 = f * H * W + y * W + x, status (2,) = [T, overflow]
+DepthCloud = collections.namedtuple("DepthCloud", "start pos pixel status")
+
+
+def tsdf_max_frames():
+    """frames one launch of the integration kernel applies (longer stacks are cut into such chunks)"""
+    return TSDF_MAX_FRAMES
+
+
+def tsdf_tile_rows():
+    """voxels (pixels) of one compaction tile of tsdf_surface and depth_unproject (tp3d_tsdf_tile_rows)"""
+    return _lib.load().tp3d_tsdf_tile_rows()
+
+
+def _depth_frames(depths, what):
+    if not torch.is_tensor(depths) or depths.dim() != 3:
+        raise ValueError("%s: the depth frames must be one (F, H, W) tensor" % what)
+    if depths.dtype in (torch.bool, torch.complex64, torch.complex128):
+        raise ValueError("%s: depth must be integer (raw) or floating (metres)" % what)
+    return depths.contiguous()
+
+
+def _depth_u16(t, what, top=None):
+    """raw integer depth as uint16 storage: negative values become 0 (no depth); wider values must not be meaningful"""
+    if t.dtype == torch.uint16:
+        return t
+    if t.dtype == torch.int16:
+        return t.clamp(min=0).view(torch.uint16)
+    if t.dtype == torch.uint8:
+        return t.to(torch.int16).view(torch.uint16)
+    if top is None or top > 65536.0:
+        raise ValueError("%s: %s depth is served as 16-bit raw depth only where max_depth * depth_scale <= 65536"
+                         % (what, t.dtype))
+    t = torch.where((t < 0) | (t > 65535), torch.zeros_like(t), t)  # beyond max_depth either way: dropped
+    return (t & 0xFFFF).to(torch.int16).view(torch.uint16)
+
+
+def tsdf_integrate(tsdf, weight, origin, voxel_size, depths, cam_intr, cam_poses, obs_weight=1.0, depth_scale=1000.0,
+                   depth_thresh=None, trunc=None):
+    """Integrates the frames depths (F, H, W), in order, into the volume tsdf, weight (X, Y, Z) fp32 IN PLACE (the
+    reference's TSDFVolume.integrate, CPU path; tsdf.py states every rule).  origin (3,) fp32 numbers, cam_intr (3, 3)
+    or (F, 3, 3), cam_poses (F, 4, 4) camera-to-world, obs_weight a number or (F,) -- all host values.  Integer depth is
+    raw: metres = double(raw) / depth_scale, zeroed above depth_thresh (None: no threshold); floating depth is metres,
+    used as given.  trunc defaults to 5 voxels.  On the device one launch applies up to tsdf_max_frames() frames to every
+    voxel in registers (uint16 / int16 and float64 frames are read in place; other types go through a float64 copy of the
+    stack); CPU tensors are served by tsdf.integrate_numpy.  Returns (tsdf, weight)."""
+    from . import tsdf as _tsdf
+    if tsdf.dim() != 3 or tsdf.shape != weight.shape or tsdf.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise ValueError("tsdf_integrate: tsdf and weight must be fp32 volumes (X, Y, Z) of one shape")
+    if not tsdf.is_contiguous() or not weight.is_contiguous():
+        raise ValueError("tsdf_integrate: the volumes are updated in place and must be contiguous")
+    depths = _depth_frames(depths, "tsdf_integrate")
+    F, H, W = depths.shape
+    origin = np.asarray(origin, dtype=np.float32).reshape(3)
+    vs = float(voxel_size)
+    trunc = _tsdf.TRUNC_VOXELS * vs if trunc is None else float(trunc)
+    if not (vs > 0.0 and trunc > 0.0 and float(depth_scale) > 0.0):
+        raise ValueError("tsdf_integrate: voxel_size, trunc and depth_scale must be positive")
+    consts = _tsdf.integrate_consts(cam_intr, cam_poses, obs_weight, F)
+    raw = not depths.dtype.is_floating_point
+    if tsdf.device.type != "cuda":
+        if depths.device.type != "cpu":
+            raise ValueError("tsdf_integrate: the volume and the frames must be on one device")
+        d = depths.numpy() if depths.dtype != torch.bfloat16 else depths.float().numpy()
+        t, w = tsdf.numpy(), weight.numpy()
+        for f in range(F):
+            metres = _tsdf.depth_metres_numpy(d[f], depth_scale, depth_thresh) if raw else d[f].astype(np.float64)
+            _tsdf.integrate_numpy(t, w, origin, vs, metres, consts[f], trunc)
+        return tsdf, weight
+    dev = _dev(tsdf, weight, depths)
+    thresh = float("inf") if depth_thresh is None else float(depth_thresh)
+    if depths.dtype in (torch.uint16, torch.int16, torch.uint8):
+        depths, kind = _depth_u16(depths, "tsdf_integrate"), 0
+    elif raw:
+        d = _tsdf.true_divide(depths, depth_scale)  # an IEEE division, not torch's multiplication by the reciprocal
+        depths, kind = torch.where(d > thresh, torch.zeros_like(d), d), 1
+    else:
+        depths, kind = depths.to(torch.float64), 1
+    if F == 0 or tsdf.numel() == 0:
+        return tsdf, weight
+    c = torch.from_numpy(consts).to(dev)
+    X, Y, Z = tsdf.shape
+    with _lib.on_device(dev):
+        for f0 in range(0, F, TSDF_MAX_FRAMES):
+            n = min(TSDF_MAX_FRAMES, F - f0)
+            _lib.call("tp3d_tsdf_integrate", _lib.ptr(tsdf), _lib.ptr(weight), X, Y, Z, float(origin[0]), float(origin[1]),
+                      float(origin[2]), vs, trunc, _lib.ptr(depths[f0:f0 + n]), kind, n, H, W, _lib.ptr(c[f0:f0 + n]),
+                      float(depth_scale), thresh, _lib.stream_ptr(dev))
+    return tsdf, weight
+
+
+def tsdf_surface(tsdf, weight, origin, voxel_size, tsdf_thresh, weight_thresh, capacity=None, with_index=True):
+    """The surface cloud of a volume (TSDFVolume.get_point_cloud): the voxels with |t| < tsdf_thresh and w > weight_thresh
+    (fp32 compares) in ascending voxel index, as float64 index * voxel_size + double(origin), with their flat voxel ids.
+    capacity=None: exact arrays, one integer read back.  capacity=c: nothing is read back, the arrays have c rows of which
+    the first min(T, c) are meaningful, status = [T, T > c] on the device.  Returns a TsdfSurface.  The predicate is
+    evaluated on the fly by a count and an emit pass; no mask of volume size exists at any time."""
+    from . import tsdf as _tsdf
+    if tsdf.dim() != 3 or tsdf.shape != weight.shape or tsdf.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise ValueError("tsdf_surface: tsdf and weight must be fp32 volumes (X, Y, Z) of one shape")
+    origin = np.asarray(origin, dtype=np.float32).reshape(3)
+    vs = float(voxel_size)
+    N = tsdf.numel()
+    if N > TSDF_MAX_VOXELS:
+        raise ValueError("tsdf_surface serves at most 2^31 - 1 voxels")
+    if capacity is not None and not (0 <= int(capacity) <= TSDF_MAX_VOXELS):
+        raise ValueError("capacity must lie in [0, 2^31)")
+    if tsdf.device.type != "cuda":
+        pos, index = _tsdf.surface_numpy(tsdf.numpy(), weight.numpy(), origin, vs, tsdf_thresh, weight_thresh)
+        parts, status = _cut_to_capacity([torch.from_numpy(pos), torch.from_numpy(index)], capacity)
+        if capacity is not None and parts[0].shape[0] < int(capacity):  # the fixed-size form: zero rows behind the list
+            pad = int(capacity) - parts[0].shape[0]
+            parts = [torch.cat([parts[0], torch.zeros((pad, 3), dtype=torch.float64)]),
+                     torch.cat([parts[1], torch.zeros((pad,), dtype=torch.int64)])]
+        return TsdfSurface(parts[0], parts[1] if with_index else None, status)
+    dev = _dev(tsdf, weight)
+    tsdf, weight = tsdf.contiguous(), weight.contiguous()
+    X, Y, Z = tsdf.shape
+    tt, wt = float(np.float32(tsdf_thresh)), float(np.float32(weight_thresh))
+    status = torch.empty((2,), dtype=torch.int64, device=dev)
+    nbytes = _lib.load().tp3d_tsdf_surface_workspace_bytes(N)
+    ws = _lib.workspace("tsdf_compact", nbytes, dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_tsdf_surface_count", _lib.ptr(tsdf), _lib.ptr(weight), N, tt, wt,
+                  -1 if capacity is None else int(capacity), _lib.ptr(status), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+    cap = int(status[0]) if capacity is None else int(capacity)  # the one device-to-host read
+    new = torch.empty if capacity is None else torch.zeros
+    pos = new((cap, 3), dtype=torch.float64, device=dev)
+    index = new((cap,), dtype=torch.int64, device=dev) if with_index else None
+    with _lib.on_device(dev):
+        _lib.call("tp3d_tsdf_surface_emit", _lib.ptr(tsdf), _lib.ptr(weight), X, Y, Z, float(origin[0]), float(origin[1]),
+                  float(origin[2]), vs, tt, wt, cap, _lib.ptr(pos), _lib.ptr(index), _lib.ptr(ws), nbytes,
+                  _lib.stream_ptr(dev))
+    return TsdfSurface(pos, index, status)
+
+
+def depth_unproject(depths, cam_intr, cam_poses=None, depth_scale=1000.0, max_depth=6.0, capacity=None, with_pos=True):
+    """The world points of F raw depth frames (F, H, W) as one ragged list (the reference's extract_pcd + rgbd2pcd, frame
+    after frame): Z = raw / depth_scale, kept for (Z < max_depth) & (Z > 0) in ascending pixel index;
+    X = ((x + 0.5) - K02) * Z / K00, Y likewise; world = ((X r_a0 + Y r_a1) + Z r_a2) + t_a in double.  cam_intr (3, 3) or
+    (F, 3, 3) and cam_poses (F, 4, 4) (None: camera coordinates) are host values.  Returns a DepthCloud: start (F + 1,),
+    pos (T, 3) float64, pixel (T,) = f * H * W + y * W + x for gathering colour rows; capacity as in tsdf_surface."""
+    from . import tsdf as _tsdf
+    depths = _depth_frames(depths, "depth_unproject")
+    if depths.dtype.is_floating_point:
+        raise ValueError("depth_unproject takes raw integer depth")
+    F, H, W = depths.shape
+    if F * H * W > TSDF_MAX_VOXELS:
+        raise ValueError("depth_unproject serves at most 2^31 - 1 pixels per call")
+    if capacity is not None and not (0 <= int(capacity) <= TSDF_MAX_VOXELS):
+        raise ValueError("capacity must lie in [0, 2^31)")
+    if not float(depth_scale) > 0.0:
+        raise ValueError("depth_unproject: depth_scale must be positive")
+    consts = _tsdf.unproject_consts(cam_intr, cam_poses, F)
+    if depths.device.type != "cuda":
+        d = depths.numpy()
+        start, pos, pixel = _tsdf.unproject_numpy(d, consts, depth_scale, max_depth)
+        parts, status = _cut_to_capacity([torch.from_numpy(pos), torch.from_numpy(pixel)], capacity)
+        if capacity is not None and parts[0].shape[0] < int(capacity):
+            pad = int(capacity) - parts[0].shape[0]
+            parts = [torch.cat([parts[0], torch.zeros((pad, 3), dtype=torch.float64)]),
+                     torch.cat([parts[1], torch.zeros((pad,), dtype=torch.int64)])]
+        return DepthCloud(torch.from_numpy(start), parts[0] if with_pos else None, parts[1], status)
+    dev = depths.device
+    d16 = _depth_u16(depths, "depth_unproject", float(max_depth) * float(depth_scale))
+    start = torch.empty((F + 1,), dtype=torch.int64, device=dev)
+    status = torch.empty((2,), dtype=torch.int64, device=dev)
+    nbytes = _lib.load().tp3d_depth_unproject_workspace_bytes(F, H * W)
+    ws = _lib.workspace("tsdf_compact", nbytes, dev)
+    c = torch.from_numpy(consts).to(dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_depth_unproject_count", _lib.ptr(d16), F, H, W, float(depth_scale), float(max_depth),
+                  -1 if capacity is None else int(capacity), _lib.ptr(start), _lib.ptr(status), _lib.ptr(ws), nbytes,
+                  _lib.stream_ptr(dev))
+    cap = int(status[0]) if capacity is None else int(capacity)  # the one device-to-host read
+    new = torch.empty if capacity is None else torch.zeros
+    pos = new((cap, 3), dtype=torch.float64, device=dev) if with_pos else None
+    pixel = new((cap,), dtype=torch.int64, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("tp3d_depth_unproject_emit", _lib.ptr(d16), F, H, W, _lib.ptr(c), float(depth_scale), float(max_depth), cap,
+                  _lib.ptr(pos), _lib.ptr(pixel), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+    return DepthCloud(start, pos, pixel, status)
